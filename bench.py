@@ -2,6 +2,21 @@
 """Benchmark of the CG hot path (BASELINE.json metric) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 256] [--weak]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it sets up,
+warms up, times the K steps, writes its outputs when --dump-outputs is given
+and prints the result line. Everything else described below (the per-kernel
+roofline pass and its PMC traffic, `csr_general`, `cpu_baseline`, the RCCL
+iteration timed beside the peer transport) runs only with --full.
+
+--dump-outputs DIR writes what the timed run computed, right after its last
+step: `x.npy`, the solution vector the K-th timed body leaves in the caller's
+x (float64; a fixed, seeded sample of 2^20 entries where x is longer:
+dump_sample), and `rxr.npy` (r.r after that body, float64).
+The inputs are the same in every run (generated matrix, b_i = i + 1, x0 = 0),
+so two builds can be compared output for output. At N > 1 every rank writes
+its own rows' files with a `_rank<r>` suffix.
 
 A "step" is one CG iteration (loop body of CG::solve, src/CG.hpp:359-436):
 SpMV + p.Ap, r-update + r.r, x/p-update, on synthetic 3-D 7-point Dirichlet
@@ -32,10 +47,10 @@ iteration_frac = achieved_GBs / (peak x N). The CSR-priced figure of SURVEY
 `csr_equivalent_GBs`.
 
 The timed region replays hipGraphs of the iteration (no per-kernel events).
-Right after it, `--profile-steps` more iterations run with HIP events around
+With --full, right after it `--profile-steps` more iterations run with HIP events around
 every kernel on the solver stream (the stream the kernels run on); rank 0
 reports the dominant kernel's roofline (k_spmv_dot) from those, priced at
-its own format's compulsory bytes. At N = 1 rank 0 also reports:
+its own format's compulsory bytes. At N = 1 rank 0 then also reports:
   * `csr_general`: the same 256^3 matrix solved with the general-value
     formats (plain SELL-P values, and CSR-stream — the path of a matrix with
     many distinct values such as G3_circuit);
@@ -115,6 +130,14 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not "
+                         "need: the per-kernel roofline pass (--profile-steps) and its PMC "
+                         "traffic, csr_general, cpu_baseline, and at N > 1 the RCCL iteration "
+                         "beside the peer transport (each still has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed run computed in its last step as DIR/<name>.npy "
+                         "(x, a fixed seeded sample of it where it is long, and rxr)")
     ap.add_argument("--workload", default="p3d_256",
                     choices=["p3d_256", "p3d_512", "p2d_4096", "p2d_128", "g3_standin"],
                     help="BASELINE.json configuration (conjugategradient_amd/workloads.py); "
@@ -394,6 +417,39 @@ def rccl_timing(L, q, args, wl, b, x, transport, its, elapsed, world, dist) -> d
                     "stream; dots: ncclAllReduce), no device peer transport"}
 
 
+DUMP_SAMPLE = 1 << 20  # entries of x that --dump-outputs keeps (8 MB of float64)
+
+
+def dump_sample(n: int):
+    """Positions of an n-vector that --dump-outputs writes: None (all of it)
+    up to DUMP_SAMPLE entries, else DUMP_SAMPLE sorted positions drawn with a
+    fixed seed (the same in every run and build; a position may repeat)."""
+    import numpy as np
+
+    if n <= DUMP_SAMPLE:
+        return None
+    return np.sort(np.random.default_rng(256).integers(0, n, DUMP_SAMPLE))
+
+
+def dump_outputs(L, cg, x, dirname: str, rank: int, world: int) -> None:
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step, as DIR/<name>.npy (float64): x (cgx_cg_run applied every deferred x
+    update before it returned; dump_sample of it) and rxr (cgx_cg_rxr)."""
+    import numpy as np
+
+    from conjugategradient_amd._native import check
+
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    xs = x.download()
+    idx = dump_sample(len(xs))
+    rxr = C.c_double(0.0)
+    check(L.cgx_cg_rxr(cg, C.byref(rxr)))
+    np.save(os.path.join(dirname, f"x{sfx}.npy"),
+            np.ascontiguousarray(xs if idx is None else xs[idx], dtype=np.float64))
+    np.save(os.path.join(dirname, f"rxr{sfx}.npy"), np.array([rxr.value], dtype=np.float64))
+
+
 # ---------------------------------------------------------------------------
 # the measured run (one rank)
 # ---------------------------------------------------------------------------
@@ -406,6 +462,9 @@ def run(args) -> None:
     from conjugategradient_amd import workloads
     from conjugategradient_amd._native import F64, check, lib
 
+    if not args.full:  # a plain run: the headline figure only
+        args.profile_steps = 0
+        args.no_cpu = args.no_general = args.no_traffic = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -601,10 +660,12 @@ def run(args) -> None:
     if ran != args.steps:
         raise RuntimeError(f"ran {ran} iterations, expected {args.steps} (stopped={stopped.value})")
     its = args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(L, cg, x, args.dump_outputs, rank, world)
     # the north star's transport (RCCL halo + all-reduces) timed beside the
-    # device peer one when the peer transport carried the run
+    # device peer one when the peer transport carried the run (--full)
     rccl_iteration = None
-    if dist_on:
+    if dist_on and args.full:
         rccl_iteration = rccl_timing(L, q, args, wl, b, x, transport, its, elapsed, world, dist)
 
     # compulsory bytes of one iteration in the streamed formats, all ranks

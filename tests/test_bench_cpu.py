@@ -18,6 +18,28 @@ def test_defaults_are_strong_scaling_of_256():
     assert bench.parse(["--weak"]).weak
 
 
+def test_plain_run_is_the_default():
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not a.full and a.dump_outputs is None and a.steps == 20 and a.warmup == 5
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs keeps all of a short x and the same DUMP_SAMPLE sorted
+    positions of a long one in every run: float64 files of 8 MB at most."""
+    import numpy as np
+
+    assert bench.dump_sample(1) is None and bench.dump_sample(bench.DUMP_SAMPLE) is None
+    n = 256 ** 3
+    i, j = bench.dump_sample(n), bench.dump_sample(n)
+    np.testing.assert_array_equal(i, j)
+    assert len(i) == bench.DUMP_SAMPLE and 8 * len(i) <= 64 << 20
+    assert i.min() >= 0 and i.max() < n and np.all(np.diff(i) >= 0)
+    # spread over the whole vector, not a prefix
+    assert i[0] < n // 1000 and i[-1] > n - n // 1000
+
+
 def test_launcher_starts_n_ranks(monkeypatch):
     seen = {}
 

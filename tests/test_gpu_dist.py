@@ -262,7 +262,7 @@ def test_bench_two_ranks_validates_peer_transport():
     one-GPU box the setup transport is the host one (--transport host-peer);
     on an 8-GPU node it is RCCL (--transport auto)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--grid", "64",
-           "--steps", "20", "--warmup", "5", "--transport", "host-peer", "--no-cpu",
+           "--steps", "20", "--warmup", "5", "--transport", "host-peer", "--full", "--no-cpu",
            "--profile-steps", "0", "--master-port", str(_port())]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -345,8 +345,8 @@ def test_bench_rccl_iteration_at_world_size_one():
     communicator (the all-reduces run, no halo), timed as the line's value
     and reported as its rccl_iteration."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--grid", "64",
-           "--steps", "20", "--warmup", "5", "--transport", "rccl", "--no-cpu", "--no-general",
-           "--profile-steps", "0"]
+           "--steps", "20", "--warmup", "5", "--transport", "rccl", "--full", "--no-cpu",
+           "--no-general", "--profile-steps", "0"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

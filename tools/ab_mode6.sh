@@ -6,7 +6,7 @@ out=${1:-gpurun_out/ab6}
 mkdir -p $out
 for rep in 1 2; do
   for m in 3 6; do
-    timeout -k 10 240 python -u bench.py --mode $m --steps 400 --warmup 20 --no-cpu --no-general \
+    timeout -k 10 240 python -u bench.py --mode $m --steps 400 --warmup 20 --full --no-cpu --no-general \
       --no-traffic --profile-steps 100 > $out/mode${m}_rep${rep}.json 2> $out/mode${m}_rep${rep}.err || exit 1
   done
 done

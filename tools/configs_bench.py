@@ -41,7 +41,7 @@ def main():
         steps, warm, prof = PLAN[name]
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", name,
                "--steps", str(steps), "--warmup", str(warm), "--profile-steps", str(prof),
-               "--no-cpu", "--no-general", "--mode", str(a.mode)]
+               "--full", "--no-cpu", "--no-general", "--mode", str(a.mode)]
         if a.no_traffic:
             cmd.append("--no-traffic")
         p = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=900)
