@@ -107,6 +107,10 @@ _SIGS = {
     "cgx_cg_coop_trace": (_i32, [_vp, C.POINTER(C.c_uint64), _i64]),
     "cgx_cg_get_mode": (_i32, [_vp, C.POINTER(_i32)]),
     "cgx_csr_fd_grid": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "cgx_csr_diag_inv": (_i32, [_vp, _vp]),
+    "cgx_cg_set_precond": (_i32, [_vp, _i32, _vp]),
+    "cgx_cg_get_precond": (_i32, [_vp, C.POINTER(_i32)]),
+    "cgx_cg_rz": (_i32, [_vp, C.POINTER(_dbl)]),
     "cgx_accuracy": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_dbl)]),
     "cgx_poisson_nnz": (_i64, [_i32, _i32, _i32, _i32, _i64, _i64]),
     "cgx_poisson_fill": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),

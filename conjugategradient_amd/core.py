@@ -27,6 +27,13 @@ class Debuglevel(enum.IntEnum):
     Verbose = 1
 
 
+class Preconditioner(enum.IntEnum):
+    """Extension (cgx.h CGX_PRECOND_*): diagonal preconditioning of CG.solve."""
+    None_ = 0
+    Jacobi = 1     # 1 / diag(A), built on the device
+    Diagonal = 2   # a positive vector the caller supplies
+
+
 def _dtype_code(dtype) -> int:
     dt = np.dtype(dtype)
     if dt == np.float64:
@@ -171,6 +178,14 @@ class Matrix:
                                        _dtype_code(self.dtype), hr, C.byref(h)))
             self._csr = h
         return self._csr
+
+    def diag_inv(self) -> np.ndarray:
+        """Extension: 1 / a_ii (a row's entries with col == row summed), formed
+        on the device by cgx_csr_diag_inv — Jacobi's m. Raises CgxError when a
+        row has no positive, finite diagonal."""
+        out = DeviceArray(self._queue, self._N, self.dtype)
+        check(lib().cgx_csr_diag_inv(self.schedule(), out.ptr))
+        return out.download()
 
     def data(self):
         return self._data
@@ -357,6 +372,9 @@ class CG:
         self._cg_for = None
         self.iterations = 0       # extension: loop bodies of the last solve
         self.final_rxr = float("nan")  # extension: rxr after the last body
+        self.final_rz = float("nan")   # extension: r.z after the last body (preconditioned)
+        self._precond = Preconditioner.None_
+        self._minv = None  # the caller's diagonal (a Vector), kept alive for the solver
         self.poll_every = 32
         self.use_graph = True
         self.mode = 0  # cgx_cg_set_mode: 0 auto (5, 4, 6 or 3), 1 three kernels, 2 fused,
@@ -405,6 +423,39 @@ class CG:
         """:235 (empty in the reference)."""
         return None
 
+    def setPreconditioner(self, kind, diag=None) -> None:
+        """Extension: diagonal preconditioning of the following solves (modes
+        1 and 3; auto resolves to 3; the stop rule still tests the true r.r).
+        ``Jacobi`` builds 1 / diag(A) on the device, from the matrix in place
+        at each solve; ``Diagonal`` takes ``diag``, N positive finite values
+        as a numpy array or a device Vector, kept alive by this object.
+        ValueError for an unknown kind, a missing ``diag`` or a wrong length."""
+        try:
+            kind = Preconditioner(kind)
+        except (ValueError, TypeError):
+            raise ValueError(f"unknown preconditioner kind {kind!r}") from None
+        minv = None
+        if kind == Preconditioner.Diagonal:
+            if diag is None:
+                raise ValueError("Preconditioner.Diagonal needs diag")
+            n = diag.N() if isinstance(diag, Vector) else int(np.size(diag))
+            if self.A.N() and n != self.A.N():
+                raise ValueError(f"diag has {n} entries, the matrix {self.A.N()} rows")
+            if n == 0:
+                raise ValueError("diag is empty")
+            minv = diag if isinstance(diag, Vector) else Vector(self._queue, np.asarray(diag),
+                                                                dtype=self.dtype)
+        self._precond, self._minv = kind, minv
+        if self._cg is not None and self._cg_for == self.A._csr:
+            self._apply_precond()
+
+    def _apply_precond(self) -> None:
+        if self._precond == Preconditioner.Diagonal and self._minv.N() != self.A.N():
+            raise ValueError(f"diag has {self._minv.N()} entries, the matrix {self.A.N()} rows")
+        check(lib().cgx_cg_set_precond(
+            self._cg, int(self._precond),
+            self._minv.ptr() if self._precond == Preconditioner.Diagonal else None))
+
     # -- solve ----------------------------------------------------------
     def _drop_solver(self):
         if self._cg:  # valid after Queue.close (see Matrix._drop_schedule)
@@ -422,6 +473,8 @@ class CG:
             self._cg_for = sched
             check(lib().cgx_cg_config(self._cg, self.poll_every, 1 if self.use_graph else 0))
             check(lib().cgx_cg_set_mode(self._cg, self.mode))
+            if self._precond != Preconditioner.None_:
+                self._apply_precond()
         return self._cg
 
     def solve(self, improvement: float = 0.0, max_iter: int = -1) -> None:
@@ -440,6 +493,11 @@ class CG:
                                  int(max_iter), C.byref(bodies), C.byref(rxr)))
         self.iterations = bodies.value
         self.final_rxr = rxr.value
+        self.final_rz = float("nan")
+        if self._precond != Preconditioner.None_:
+            rz = C.c_double(0)
+            check(lib().cgx_cg_rz(self._cg, C.byref(rz)))
+            self.final_rz = rz.value
         self.is_solved = True
 
     # -- outputs --------------------------------------------------------

@@ -85,7 +85,11 @@ struct DeviceGuard {
 template <typename T> int enqueue_iter(cgx_cg *cg, int slot);
 
 int poll_state(cgx_cg *cg, void *h_dst, hipStream_t s) {
-  const size_t bytes = cg->dtype == CGX_F32 ? sizeof(CgScalars<float>) : sizeof(CgScalars<double>);
+  // up to rz (read by cgx_cg_rz alone): the copy's size before preconditioning,
+  // within the 256 bytes each of cgx_cg_run's two staging buffers has
+  const size_t bytes =
+      cg->dtype == CGX_F32 ? offsetof(CgScalars<float>, rz) : offsetof(CgScalars<double>, rz);
+  static_assert(offsetof(CgScalars<double>, rz) <= 256, "poll staging buffers are 256 bytes");
   CGX_HIP(hipMemcpyAsync(h_dst, cg->st, bytes, hipMemcpyDeviceToHost, s));
   return CGX_OK;
 }
@@ -323,6 +327,16 @@ template <typename T> int enqueue_iter(cgx_cg *cg, int slot) {
   const PeerDev *far = fused_ar(cg);
   const bool sep = A->dist && !far;  // a separate all-reduce step per dot
   if ((rc = enqueue_spmv_dot<T>(cg, p, slot, par, &npp))) return rc;
+  if (cg->precond) {  // single device (cgx_cg_set_precond): the SpMV launch is the plain one
+    const T *m = (const T *)cg->minv;
+    if ((rc = timed(cg, 2, s, [&] {
+           return Launch<T>::update_r_pc(cg->n, r, Ap, m, st, slot, ws, s, npp, rpar, cg->minv_nt);
+         })))
+      return rc;
+    return timed(cg, 3, s, [&] {
+      return Launch<T>::update_xp_pc(cg->n, x, p, r, m, st, slot, ws, npr, s, par, cg->minv_nt);
+    });
+  }
   if (sep && (rc = dist_dot<T>(cg, ws->pap_part, npp, &st->pAp[slot], slot, 1))) return rc;
   if ((rc = timed(cg, 2, s, [&] {
          return Launch<T>::update_r(cg->n, r, Ap, st, slot, ws, s, false, sep ? 0 : npp, rpar,
@@ -373,6 +387,17 @@ template <typename T> int enqueue_iter_defer(cgx_cg *cg, int slot) {
     });
   }
   if ((rc = enqueue_spmv_dot<T>(cg, p, slot, par, &npp))) return rc;
+  if (cg->precond) {  // single device (cgx_cg_set_precond): the SpMV launch is the plain one
+    const T *m = (const T *)cg->minv;
+    if ((rc = timed(cg, 2, s, [&] {
+           return Launch<T>::update_r_pc(cg->n, r, Ap, m, st, slot, ws, s, npp, rpar, cg->minv_nt);
+         })))
+      return rc;
+    return timed(cg, 3, s, [&] {
+      return Launch<T>::update_p_defer_pc(cg->n, x, p, pn, P, r, m, st, slot, ws, npr, s, par,
+                                          cg->minv_nt);
+    });
+  }
   if (sep && (rc = dist_dot<T>(cg, ws->pap_part, npp, &st->pAp[slot], slot, 1))) return rc;
   if ((rc = timed(cg, 2, s, [&] {
          return Launch<T>::update_r(cg->n, r, Ap, st, slot, ws, s, false, sep ? 0 : npp, rpar,
@@ -3080,6 +3105,10 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
               "mode %d: 0 auto, 1 three kernels, 2 fused, 3 three kernels with deferred x, "
               "4 fused with deferred x, 5 persistent body, 6 recomputed Ap, 7 fused with "
               "recomputed Ap", mode);
+  const int mode_req = mode;
+  CGX_REQUIRE(!cg->precond || mode == 0 || mode == 1 || mode == 3, CGX_EUNSUPPORTED,
+              "mode %d with a preconditioner set: diagonal preconditioning runs in modes 1 and 3 "
+              "(auto resolves to 3)", mode);
   CGX_REQUIRE(mode != 6 || (!cg->A->dist && vl_whole(cg->A->dev)), CGX_EUNSUPPORTED,
               "mode 6 (recomputed Ap) needs the lean stencil walk on a single device");
   CGX_REQUIRE(mode != 7 || (!cg->A->dist && cg->dtype == CGX_F64 && lean_tile_ok(cg->A->dev)),
@@ -3132,7 +3161,9 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
                   (cg->dtype == CGX_F64 && Launch<double>::fd_supported(cg->A->dev)),
               CGX_EUNSUPPORTED, "mode 4 needs an f64 matrix in a production SpMV format "
               "(variant %d has no fused kernel)", launch_variant(cg->A->dev, cg->dtype));
-  if (mode == 0) {
+  if (mode == 0 && cg->precond) {
+    mode = 3;  // the preconditioned kernels are modes 1 and 3's, whatever the matrix
+  } else if (mode == 0) {
     mode = coop_auto(cg) ? 5 : fd_auto(cg) ? 4 : 3;
     if (mode == 5) coop_r = coop_rows_per_thread(cg->n, kCoopMaxG);
     if (mode != 5 || coop_r == 0) {
@@ -3195,6 +3226,117 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
   cg->defer = d;
   cg->fdefer = fd;
   cg->recompute = rc6;
+  cg->mode_req = mode_req;
+  return CGX_OK;
+}
+
+// ===========================================================================
+// diagonal preconditioning
+// ===========================================================================
+namespace {
+// run `launch(bad)` on a {count, lowest index} pair preset to {0, ~0}, drain
+// the stream and read the pair back
+template <class F> int pc_scan(cgx_ctx *ctx, unsigned long long (&h)[2], F &&launch) {
+  unsigned long long *bad = nullptr;
+  CGX_HIP(hipMalloc((void **)&bad, sizeof(h)));
+  h[0] = 0;
+  h[1] = ~0ull;
+  hipError_t e = hipMemcpyAsync(bad, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // h is pageable: copied by now
+  if (e == hipSuccess) e = launch(bad);
+  if (e == hipSuccess) e = hipMemcpyAsync(h, bad, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(bad);
+  CGX_HIP(e);
+  return CGX_OK;
+}
+}  // namespace
+
+extern "C" int cgx_csr_diag_inv(cgx_csr *A, void *d_out) {
+  CGX_REQUIRE(A && d_out, CGX_EINVAL, "NULL argument");
+  CGX_REQUIRE(!A->dist, CGX_EUNSUPPORTED,
+              "cgx_csr_diag_inv: a partitioned matrix (diagonal preconditioning runs on a single "
+              "device, modes 1 and 3)");
+  if (A->dev.n == 0) return CGX_OK;
+  DeviceGuard g(A->ctx->device);
+  hipStream_t s = A->ctx->stream;
+  unsigned long long h[2];
+  int rc = pc_scan(A->ctx, h, [&](unsigned long long *bad) {
+    return A->dtype == CGX_F32 ? Launch<float>::diag_inv(A->dev, (float *)d_out, bad, s)
+                               : Launch<double>::diag_inv(A->dev, (double *)d_out, bad, s);
+  });
+  if (rc) return rc;
+  CGX_REQUIRE(h[0] == 0, CGX_EINVAL,
+              "cgx_csr_diag_inv: %llu row(s) without a positive, finite diagonal entry; the first "
+              "is row %llu", h[0], h[1]);
+  return CGX_OK;
+}
+
+extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
+  CGX_REQUIRE(cg, CGX_EINVAL, "cg is NULL");
+  CGX_REQUIRE(kind == CGX_PRECOND_NONE || kind == CGX_PRECOND_JACOBI ||
+                  kind == CGX_PRECOND_DIAGONAL,
+              CGX_EINVAL, "preconditioner kind %d: 0 none, 1 Jacobi, 2 a caller's diagonal", kind);
+  DeviceGuard g(cg->ctx->device);
+  hipStream_t s = cg->ctx->stream;
+  void *own = nullptr;
+  const void *m = nullptr;
+  if (kind != CGX_PRECOND_NONE) {
+    int cur = 0;
+    (void)cgx_cg_get_mode(cg, &cur);
+    CGX_REQUIRE(!cg->A->dist, CGX_EUNSUPPORTED,
+                "a preconditioner on a partitioned matrix: diagonal preconditioning runs on a "
+                "single device, in modes 1 and 3");
+    CGX_REQUIRE(cg->mode_req == 0 || cg->mode_req == 1 || cg->mode_req == 3, CGX_EUNSUPPORTED,
+                "a preconditioner in mode %d: diagonal preconditioning runs in modes 1 and 3 "
+                "(auto resolves to 3)", cur);
+    const size_t es = dtype_size(cg->dtype);
+    unsigned long long h[2];
+    int rc;
+    if (kind == CGX_PRECOND_JACOBI) {
+      // one slack element, as r and Ap have
+      CGX_HIP(hipMalloc(&own, ((size_t)cg->n + 1) * es));
+      rc = cgx_csr_diag_inv(cg->A, own);
+      m = own;
+    } else {
+      CGX_REQUIRE(d_minv, CGX_EINVAL, "CGX_PRECOND_DIAGONAL needs d_minv");
+      CGX_REQUIRE(((uintptr_t)d_minv & 15) == 0, CGX_EINVAL,
+                  "d_minv must be 16-byte aligned (the kernels read it in 16-byte lanes)");
+      rc = pc_scan(cg->ctx, h, [&](unsigned long long *bad) {
+        return cg->dtype == CGX_F32
+                   ? Launch<float>::diag_check(cg->n, (const float *)d_minv, bad, s)
+                   : Launch<double>::diag_check(cg->n, (const double *)d_minv, bad, s);
+      });
+      if (!rc && h[0] != 0) {
+        set_error("cgx_cg_set_precond: %llu entr%s of d_minv not positive and finite; the first "
+                  "is entry %llu", h[0], h[0] == 1 ? "y" : "ies", h[1]);
+        rc = CGX_EINVAL;
+      }
+      m = d_minv;
+    }
+    if (rc) {
+      if (own) (void)hipFree(own);
+      return rc;
+    }
+  }
+  // the solve in progress ends here; nothing queued may still read the old m
+  CGX_HIP(hipStreamSynchronize(s));
+  drop_graph(cg);
+  cg->begun = false;
+  if (cg->minv_own) (void)hipFree(cg->minv_own);
+  cg->minv_own = own;
+  cg->minv = m;
+  cg->precond = kind;
+  const char *e = std::getenv("CGX_PCG_M_NT");
+  cg->minv_nt = e && std::atoi(e) != 0;
+  // auto mode depends on the preconditioner (3 with one, the matrix's own without)
+  if (cg->mode_req == 0) return cgx_cg_set_mode(cg, 0);
+  return CGX_OK;
+}
+
+extern "C" int cgx_cg_get_precond(cgx_cg *cg, int *kind) {
+  CGX_REQUIRE(cg && kind, CGX_EINVAL, "NULL argument");
+  *kind = cg->precond;
   return CGX_OK;
 }
 
@@ -3230,7 +3372,7 @@ extern "C" int cgx_cg_destroy(cgx_cg *cg) {
   for (hipEvent_t e : cg->run_ev)
     if (e) (void)hipEventDestroy(e);
   for (void *p : {cg->r, cg->p, cg->p2, cg->Ap, cg->st, cg->ws, cg->pk[0], cg->pk[1], cg->pk[2],
-                  cg->coop_ws, cg->coop_trace})
+                  cg->coop_ws, cg->coop_trace, cg->minv_own})
     if (p) (void)hipFree(p);
   cgx_csr *A = cg->A;
   cgx_ctx *ctx = cg->ctx;
@@ -3299,15 +3441,32 @@ extern "C" int cgx_cg_begin(cgx_cg *cg, const void *b, void *x, double tol,
     if (rc) return rc;
     xe = cg->Ap;
   }
+  CGX_REQUIRE(!cg->precond || (!A->dist && !cg->fused && !cg->fdefer && !cg->coop &&
+                               !cg->recompute && cg->minv),
+              CGX_ESTATE, "a preconditioner is set but the solver is not in mode 1 or 3");
   rc = timed(cg, 0, s, [&] {
-    if (cg->dtype == CGX_F32)
-      return Launch<float>::cg_init(A->dev, (const float *)xe, (const float *)b, (float *)cg->r,
-                                    (float *)cg->p, (CgScalars<float> *)cg->st,
-                                    (RedWs<float> *)cg->ws, (float)tol, cap, s);
-    return Launch<double>::cg_init(A->dev, (const double *)xe, (const double *)b,
-                                   (double *)cg->r, (double *)cg->p,
-                                   (CgScalars<double> *)cg->st, (RedWs<double> *)cg->ws, tol,
-                                   cap, s);
+    // with a preconditioner a second launch overwrites p = m o r and reduces
+    // rz[0] = r.(m o r) (timed with the init kernel, index 0)
+    if (cg->dtype == CGX_F32) {
+      hipError_t e = Launch<float>::cg_init(A->dev, (const float *)xe, (const float *)b,
+                                            (float *)cg->r, (float *)cg->p,
+                                            (CgScalars<float> *)cg->st, (RedWs<float> *)cg->ws,
+                                            (float)tol, cap, s);
+      if (e == hipSuccess && cg->precond)
+        e = Launch<float>::pc_init(cg->n, (const float *)cg->r, (const float *)cg->minv,
+                                   (float *)cg->p, (CgScalars<float> *)cg->st,
+                                   (RedWs<float> *)cg->ws, s);
+      return e;
+    }
+    hipError_t e = Launch<double>::cg_init(A->dev, (const double *)xe, (const double *)b,
+                                           (double *)cg->r, (double *)cg->p,
+                                           (CgScalars<double> *)cg->st, (RedWs<double> *)cg->ws,
+                                           tol, cap, s);
+    if (e == hipSuccess && cg->precond)
+      e = Launch<double>::pc_init(cg->n, (const double *)cg->r, (const double *)cg->minv,
+                                  (double *)cg->p, (CgScalars<double> *)cg->st,
+                                  (RedWs<double> *)cg->ws, s);
+    return e;
   });
   if (rc) return rc;
   if (A->dist && A->peer.on) {
@@ -3489,6 +3648,27 @@ extern "C" int cgx_cg_rxr(cgx_cg *cg, double *rxr) {
   // the rxr after the last body sits in the slot of the first skipped body
   const long long bodies = view_state(cg, h, 0).bodies;
   *rxr = view_state(cg, h, (int)(bodies & 3)).rxr;
+  return CGX_OK;
+}
+
+extern "C" int cgx_cg_rz(cgx_cg *cg, double *rz) {
+  CGX_REQUIRE(cg && rz, CGX_EINVAL, "NULL argument");
+  CGX_REQUIRE(cg->precond, CGX_ESTATE, "cgx_cg_rz without a preconditioner");
+  CGX_REQUIRE(cg->begun, CGX_ESTATE, "cgx_cg_rz before cgx_cg_begin");
+  DeviceGuard g(cg->ctx->device);
+  hipStream_t s = cg->ctx->stream;
+  auto *h = (char *)cg->ctx->h_pinned;
+  int rc;
+  if ((rc = poll_state(cg, h, s))) return rc;
+  // rz lies past the polled part of the scalars: into the staging buffer's tail
+  const bool f32 = cg->dtype == CGX_F32;
+  const size_t off = f32 ? offsetof(CgScalars<float>, rz) : offsetof(CgScalars<double>, rz);
+  CGX_HIP(hipMemcpyAsync(h + 256, (const char *)cg->st + off, 4 * dtype_size(cg->dtype),
+                         hipMemcpyDeviceToHost, s));
+  CGX_HIP(hipStreamSynchronize(s));
+  // as rxr: the value after the last body sits in the slot of the first skipped body
+  const int slot = (int)(view_state(cg, h, 0).bodies & 3);
+  *rz = f32 ? (double)((const float *)(h + 256))[slot] : ((const double *)(h + 256))[slot];
   return CGX_OK;
 }
 

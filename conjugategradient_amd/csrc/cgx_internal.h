@@ -49,6 +49,11 @@ template <typename T> struct CgScalars {
   T alpha[4];
   int ran[4];
   int skip[4];
+  // diagonal preconditioning (cgx_cg_set_precond): r.(m o r) at the start of
+  // the body in slot s, the role rxr[s] has in alpha and beta (rxr keeps the
+  // true r.r for the stop rule). Last, so the offsets above do not move; the
+  // host's polls copy the struct up to here (cgx_abi.cpp poll_state).
+  T rz[4];
 };
 
 // Grid-reduction workspace. Arrivals are sharded over kRedGroups tickets
@@ -69,6 +74,9 @@ template <typename T> struct RedWs {
   // (each partial a double-length pair hi, lo: cgx_kernels.hip Dd)
   T pap_part[4 * kMaxGrid];  // room for the interior + boundary launches of a split SpMV
   T rr_part[4 * kMaxGrid];
+  // r.(m o r) of a preconditioned body, laid out as rr_part (last: the
+  // offsets above do not move)
+  T rz_part[4 * kMaxGrid];
 };
 
 // SELL copy of a matrix (built by cgx_csr_create when the matrix qualifies,
@@ -386,6 +394,26 @@ template <typename T> struct Launch {
                                    const PeerDev *peer = nullptr);
   static hipError_t flush_defer(int64_t n, T *x, T *const P[4], CgScalars<T> *st,
                                 hipStream_t s);
+  // diagonal preconditioning (modes 1 and 3 on one device): the
+  // three vector kernels with z = m o r formed where r is in registers; m_nt:
+  // m read with non-temporal loads (an A/B switch, tools/pcg_bench.py)
+  static hipError_t pc_init(int64_t n, const T *r, const T *m, T *p, CgScalars<T> *st,
+                            RedWs<T> *ws, hipStream_t s);
+  static hipError_t update_r_pc(int64_t n, T *r, const T *Ap, const T *m, CgScalars<T> *st,
+                                int slot, RedWs<T> *ws, hipStream_t s, int np_pap, int rev,
+                                bool m_nt);
+  static hipError_t update_xp_pc(int64_t n, T *x, T *p, const T *r, const T *m,
+                                 CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr,
+                                 hipStream_t s, int rev, bool m_nt);
+  static hipError_t update_p_defer_pc(int64_t n, T *x, const T *p, T *pn, T *const P[4],
+                                      const T *r, const T *m, CgScalars<T> *st, int slot,
+                                      RedWs<T> *ws, int np_rr, hipStream_t s, int rev, bool m_nt);
+  // out[i] = 1 / (sum of row i's entries with col == i); bad[0] counts the
+  // rows whose diagonal is missing, not positive or not finite, bad[1] is the
+  // lowest such row (the caller presets {0, ~0})
+  static hipError_t diag_inv(const CsrDev &A, T *out, unsigned long long *bad, hipStream_t s);
+  // the same test over a caller's m[0..n)
+  static hipError_t diag_check(int64_t n, const T *m, unsigned long long *bad, hipStream_t s);
   static hipError_t dot_acc(int64_t n, const T *x, const T *y, T *res, RedWs<T> *ws,
                             hipStream_t s);
   static hipError_t axpby(int mode, int64_t n, const T *x, const T *y, const T *a,

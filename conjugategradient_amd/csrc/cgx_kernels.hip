@@ -4683,6 +4683,430 @@ __global__ __launch_bounds__(kBlock) void k_flush_group(int64_t n, T *__restrict
   flush_group_range<T>(n, x, P0, P1, P2, P3, a, use, rev);
 }
 
+// ---------------------------------------------------------------------------
+// Diagonal preconditioning (cgx_cg_set_precond): the vector
+// kernels of modes 1 and 3 on one device with z = m o r (m = M^-1's diagonal)
+// never stored: z_i = m_i * r_i, rounded, is formed where r_i is in a
+// register, in update_r's second dot and in the p update, the same
+// expression in both. alpha = rz / p.Ap and beta = rz' / rz with rz = r.z;
+// rxr stays the true r.r and the stop rule is the plain one. The kernels
+// mirror k_update_r, k_update_xp and k_update_p_defer statement for statement
+// (those are untouched), and r.z is accumulated and summed exactly as r.r is,
+// so with m == 1 every value is the plain solver's, bit for bit.
+// MNT: m through non-temporal loads. m is read by update_r and again by the
+// p update and never written, so the default is plain loads, which let it
+// stay in L2 / the Infinity Cache between the two (A/B: tools/pcg_bench.py).
+// ---------------------------------------------------------------------------
+
+// after k_cg_init: p = m o r and rz[0] = r.(m o r) (single device)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_pc_init(int64_t n, const T *__restrict__ r,
+                                                    const T *__restrict__ m, T *__restrict__ p,
+                                                    CgScalars<T> *st, RedWs<T> *ws) {
+  __shared__ T red[8];
+  __shared__ int flag;
+  Dd<T> acc(T(0));
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    const T rv = r[i];
+    const T z = m[i] * rv;
+    p[i] = z;
+    acc += rv * z;
+  }
+  if (grid_reduce_dd(acc, ws, red, &flag) && threadIdx.x == 0) st->rz[0] = acc.value();
+}
+
+// r = r - alpha Ap with alpha = rz / p.Ap; r.r and r.(m o r) in one sweep
+// (update_r_body's single-device, non-fused form)
+template <typename T, bool SNT, bool MNT, int KP>
+__device__ __forceinline__ void update_r_pc_body(int64_t n, T *r, const T *__restrict__ Ap,
+                                                 const T *__restrict__ m, CgScalars<T> *st,
+                                                 int slot, RedWs<T> *ws, int np_pap, int rev) {
+  const auto *cst = (const __attribute__((address_space(4))) CgScalars<T> *)st;
+  const bool act = cst->active[slot] != 0;  // branched on after the first loads
+  __shared__ T red[8];
+  __shared__ T redz[8];
+  using V = typename Vec2<T>::V;
+  const int64_t n2 = n >> 1;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  V *r2 = reinterpret_cast<V *>(r);
+  const V *a2 = reinterpret_cast<const V *>(Ap);
+  const V *m2 = reinterpret_cast<const V *>(m);
+  // the clamped first loads of n = 1 reach one element past the end: r and Ap
+  // carry a slack element, a caller's m need not, so they read r instead
+  const V *m2f = n2 > 0 ? m2 : reinterpret_cast<const V *>(r);
+  auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const T rz = cst->rz[slot];
+  Dd<T> pl[KP];
+  parts_load(ws->pap_part, np_pap, pl);
+  V rv[kUR], av[kUR], mv[kUR];
+#pragma unroll
+  for (int u = 0; u < kUR; ++u) {  // clamped: no branch
+    const int64_t j = E(min(i + u * stride, n2 > 0 ? n2 - 1 : 0));
+    rv[u] = r2[j];
+    av[u] = ldv<SNT, T>(a2 + j);  // Ap is dead after this kernel
+    mv[u] = ldv<MNT, T>(m2f + j);
+  }
+  if (!act) {
+    keep(rz);
+    keep(pl);
+    keep(rv);
+    keep(av);
+    keep(mv);
+    return;
+  }
+  const T pAp = parts_sum_dd(pl, np_pap, red).value();
+  const T alpha = rz / pAp;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {  // the record; the deferred x update
+    st->pAp[slot] = pAp;
+    st->alpha[slot] = alpha;
+    st->skip[slot] = 0;
+  }
+  Dd<T> acc(T(0)), accz(T(0));  // r.r and r.z (double-length)
+  for (bool first = true; i + (kUR - 1) * stride < n2; i += kUR * stride, first = false) {
+    if (!first) {
+#pragma unroll
+      for (int u = 0; u < kUR; ++u) {
+        rv[u] = r2[E(i + u * stride)];
+        av[u] = ldv<SNT, T>(a2 + E(i + u * stride));
+        mv[u] = ldv<MNT, T>(m2 + E(i + u * stride));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kUR; ++u) {
+      rv[u].x = rv[u].x - alpha * av[u].x;
+      rv[u].y = rv[u].y - alpha * av[u].y;
+      r2[E(i + u * stride)] = rv[u];
+      acc += rv[u].x * rv[u].x;
+      acc += rv[u].y * rv[u].y;
+      accz += rv[u].x * (mv[u].x * rv[u].x);
+      accz += rv[u].y * (mv[u].y * rv[u].y);
+    }
+  }
+  for (; i < n2; i += stride) {
+    V rv = r2[E(i)];
+    const V av = a2[E(i)];
+    const V mv = m2[E(i)];
+    rv.x = rv.x - alpha * av.x;
+    rv.y = rv.y - alpha * av.y;
+    r2[E(i)] = rv;
+    acc += rv.x * rv.x;
+    acc += rv.y * rv.y;
+    accz += rv.x * (mv.x * rv.x);
+    accz += rv.y * (mv.y * rv.y);
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const T v = r[n - 1] - alpha * Ap[n - 1];
+    r[n - 1] = v;
+    acc += v * v;
+    accz += v * (m[n - 1] * v);
+  }
+  // this workgroup's shares of the two dots; the next kernel sums them
+  acc = block_sum_dd(acc, red);
+  accz = block_sum_dd(accz, redz);
+  if (threadIdx.x == 0) {
+    ws->rr_part[2 * blockIdx.x] = acc.hi;
+    ws->rr_part[2 * blockIdx.x + 1] = acc.lo;
+    ws->rz_part[2 * blockIdx.x] = accz.hi;
+    ws->rz_part[2 * blockIdx.x + 1] = accz.lo;
+  }
+}
+template <typename T, bool MNT, int KP>
+__global__ __launch_bounds__(kBlock) void k_update_r_pc(int64_t n, T *r, const T *__restrict__ Ap,
+                                                        const T *__restrict__ m,
+                                                        CgScalars<T> *st, int slot,
+                                                        RedWs<T> *ws, int np_pap, int rev) {
+  if (stream_nt<T>(n))
+    update_r_pc_body<T, true, MNT, KP>(n, r, Ap, m, st, slot, ws, np_pap, rev);
+  else
+    update_r_pc_body<T, false, MNT, KP>(n, r, Ap, m, st, slot, ws, np_pap, rev);
+}
+
+// the stop rule and the records of a preconditioned body (workgroup 0,
+// thread 0 of its p update), as k_update_xp's
+template <typename T>
+__device__ __forceinline__ void pc_stop_rule(CgScalars<T> *st, int slot, T rxr, T rr, T rzn) {
+  const int nxt = (slot + 1) & 3;
+  st->rr[slot] = rr;  // the record
+  const long long mb = st->bodies + 1;
+  st->bodies = mb;
+  const bool cond = isnan(rxr) || sqrt(rxr) <= st->tol;
+  const bool cont = !cond && mb < st->cap;
+  st->active[nxt] = cont ? 1 : 0;
+  st->rxr[nxt] = rr;
+  st->rz[nxt] = rzn;
+  st->stopped = cond ? 1 : (cont ? 0 : 2);
+}
+
+// mode 1: x = x + alpha p ; p = m o r + beta p ; stop rule (k_update_xp)
+template <typename T, bool MNT>
+__global__ __launch_bounds__(kBlock) void k_update_xp_pc(int64_t n, T *__restrict__ x,
+                                                         T *__restrict__ p,
+                                                         const T *__restrict__ r,
+                                                         const T *__restrict__ m,
+                                                         CgScalars<T> *st, int slot,
+                                                         RedWs<T> *ws, int np_rr, int rev) {
+  const int nxt = (slot + 1) & 3;
+  if (!st->active[slot]) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->active[nxt] = 0;
+    return;
+  }
+  __shared__ T red[8];
+  __shared__ T redz[8];
+  const T rxr = st->rxr[slot];
+  const T rz = st->rz[slot];
+  const T alpha = rz / st->pAp[slot];
+  const T rr = sum_parts_dd(ws->rr_part, np_rr, red).value();
+  const T rzn = sum_parts_dd(ws->rz_part, np_rr, redz).value();
+  const T beta = rzn / rz;
+  using V = typename Vec2<T>::V;
+  const int64_t n2 = n >> 1;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  V *x2 = reinterpret_cast<V *>(x);
+  V *p2 = reinterpret_cast<V *>(p);
+  const V *rv2 = reinterpret_cast<const V *>(r);
+  const V *m2 = reinterpret_cast<const V *>(m);
+  auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  for (; i + 3 * stride < n2; i += 4 * stride) {
+    V xv[4], pv[4], rv[4], mv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      xv[u] = x2[E(i + u * stride)];
+      pv[u] = p2[E(i + u * stride)];
+      rv[u] = rv2[E(i + u * stride)];
+      mv[u] = ldv<MNT, T>(m2 + E(i + u * stride));
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      xv[u].x = xv[u].x + alpha * pv[u].x;
+      xv[u].y = xv[u].y + alpha * pv[u].y;
+      pv[u].x = mv[u].x * rv[u].x + beta * pv[u].x;
+      pv[u].y = mv[u].y * rv[u].y + beta * pv[u].y;
+      x2[E(i + u * stride)] = xv[u];
+      p2[E(i + u * stride)] = pv[u];
+    }
+  }
+  for (; i < n2; i += stride) {
+    V xv = x2[E(i)], pv = p2[E(i)];
+    const V rv = rv2[E(i)];
+    const V mv = ldv<MNT, T>(m2 + E(i));
+    xv.x = xv.x + alpha * pv.x;
+    xv.y = xv.y + alpha * pv.y;
+    pv.x = mv.x * rv.x + beta * pv.x;
+    pv.y = mv.y * rv.y + beta * pv.y;
+    x2[E(i)] = xv;
+    p2[E(i)] = pv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (n & 1) {
+      const T pv = p[n - 1];
+      x[n - 1] = x[n - 1] + alpha * pv;
+      p[n - 1] = m[n - 1] * r[n - 1] + beta * pv;
+    }
+    pc_stop_rule(st, slot, rxr, rr, rzn);
+  }
+}
+
+// mode 3: p_{k+1} = m o r + beta p_k into the next p buffer, the stop rule,
+// and in slot 3 (FLUSH) the group's x updates (update_p_defer_body's
+// single-device form; the alphas it applies are update_r_pc's rz / p.Ap)
+template <typename T, bool FLUSH, bool SNT, bool MNT>
+__device__ __forceinline__ void update_p_defer_pc_body(int64_t n, T *__restrict__ x, const T *p,
+                                                       T *pn, const T *P0, const T *P1,
+                                                       const T *P2, const T *__restrict__ r,
+                                                       const T *__restrict__ m,
+                                                       CgScalars<T> *st, int slot, RedWs<T> *ws,
+                                                       int np_rr, int rev) {
+  const int nxt = (slot + 1) & 3;
+  // the flag, rxr, rz and both dots' partials in one round trip
+  const auto *cst = (const __attribute__((address_space(4))) CgScalars<T> *)st;
+  const bool act = cst->active[slot] != 0;
+  const T rxr = cst->rxr[slot];
+  const T rz = cst->rz[slot];
+  Dd<T> pl[kPartsPerThread], plz[kPartsPerThread];
+  parts_load_np(ws->rr_part, np_rr, pl);
+  parts_load_np(ws->rz_part, np_rr, plz);
+  using V = typename Vec2<T>::V;
+  const int64_t n2 = n >> 1;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const V *p2 = reinterpret_cast<const V *>(p);
+  const V *rv2 = reinterpret_cast<const V *>(r);
+  const V *m2 = reinterpret_cast<const V *>(m);
+  // the non-flushing body: this thread's first four elements of p_k, r and m
+  // go out with the partials, before beta (clamped; for n = 1 m's load reads
+  // r, which has the slack element a caller's m need not have)
+  V pv0[4], rv0[4], mv0[4];
+  if constexpr (!FLUSH) {
+    const V *m2f = n2 > 0 ? m2 : rv2;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t j = E(min(i + u * stride, n2 > 0 ? n2 - 1 : 0));
+      pv0[u] = ldv<SNT, T>(p2 + j);
+      rv0[u] = ldv<SNT, T>(rv2 + j);
+      mv0[u] = ldv<MNT, T>(m2f + j);
+    }
+  }
+  if (!act) {
+    keep(rxr);
+    keep(rz);
+    keep(pl);
+    keep(plz);
+    if constexpr (!FLUSH) {
+      keep(pv0);
+      keep(rv0);
+      keep(mv0);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->active[nxt] = 0;
+    return;
+  }
+  __shared__ T red[8];
+  __shared__ T redz[8];
+  const T rr = parts_sum_dd(pl, np_rr, red).value();
+  const T rzn = parts_sum_dd(plz, np_rr, redz).value();
+  const T beta = rzn / rz;
+  // slot-3 flush: alphas and skips of the group, written by earlier launches
+  T a[4] = {T(0), T(0), T(0), T(0)};
+  bool use[4] = {false, false, false, false};
+  if constexpr (FLUSH) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      a[t] = st->alpha[t];
+      use[t] = st->skip[t] == 0;
+    }
+  }
+  V *pn2 = reinterpret_cast<V *>(pn);
+  V *x2 = reinterpret_cast<V *>(x);
+  const V *Q[3] = {reinterpret_cast<const V *>(P0), reinterpret_cast<const V *>(P1),
+                   reinterpret_cast<const V *>(P2)};
+  auto body = [&](int64_t i) {
+    const V pv = ldv<SNT, T>(p2 + i);
+    const V rv = ldv<SNT, T>(rv2 + i);
+    const V mv = ldv<MNT, T>(m2 + i);
+    V q[3], xv;
+    if constexpr (FLUSH) {  // x and the old p buffers: not read again soon
+      xv = ldv<SNT, T>(x2 + i);
+#pragma unroll
+      for (int t = 0; t < 3; ++t) q[t] = ldv<SNT, T>(Q[t] + i);  // before pn (= P0) is written
+    }
+    V o;
+    o.x = mv.x * rv.x + beta * pv.x;
+    o.y = mv.y * rv.y + beta * pv.y;
+    if constexpr (FLUSH) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        if (use[t]) {
+          xv.x = xv.x + a[t] * q[t].x;
+          xv.y = xv.y + a[t] * q[t].y;
+        }
+      }
+      if (use[3]) {
+        xv.x = xv.x + a[3] * pv.x;
+        xv.y = xv.y + a[3] * pv.y;
+      }
+      stv<SNT, T>(x2 + i, xv);
+    }
+    pn2[i] = o;
+  };
+  if constexpr (!FLUSH) {
+    // the first block from the early loads (a block past the end: its
+    // clamped loads are not stored)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (i + u * stride < n2) {
+        V o;
+        o.x = mv0[u].x * rv0[u].x + beta * pv0[u].x;
+        o.y = mv0[u].y * rv0[u].y + beta * pv0[u].y;
+        pn2[E(i + u * stride)] = o;
+      }
+    }
+    i += 4 * stride;
+  }
+  for (; i + 3 * stride < n2; i += 4 * stride) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) body(E(i + u * stride));
+  }
+  for (; i < n2; i += stride) body(E(i));
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (n & 1) {
+      const T pv = p[n - 1];
+      if constexpr (FLUSH) {
+        T xv = x[n - 1];
+        const T *Ps[4] = {P0, P1, P2, p};
+        for (int t = 0; t < 4; ++t)
+          if (use[t]) xv = xv + a[t] * Ps[t][n - 1];
+        x[n - 1] = xv;
+      }
+      pn[n - 1] = m[n - 1] * r[n - 1] + beta * pv;
+    }
+    pc_stop_rule(st, slot, rxr, rr, rzn);
+    if constexpr (FLUSH) {
+      for (int t = 0; t < 4; ++t) st->ran[t] = 0;
+    } else {
+      st->ran[slot] = 1;
+    }
+  }
+}
+template <typename T, bool FLUSH, bool MNT>
+__global__ __launch_bounds__(kBlock) void k_update_p_defer_pc(
+    int64_t n, T *__restrict__ x, const T *p, T *pn, const T *P0, const T *P1, const T *P2,
+    const T *__restrict__ r, const T *__restrict__ m, CgScalars<T> *st, int slot, RedWs<T> *ws,
+    int np_rr, int rev) {
+  if (stream_nt<T>(n))
+    update_p_defer_pc_body<T, FLUSH, true, MNT>(n, x, p, pn, P0, P1, P2, r, m, st, slot, ws,
+                                                np_rr, rev);
+  else
+    update_p_defer_pc_body<T, FLUSH, false, MNT>(n, x, p, pn, P0, P1, P2, r, m, st, slot, ws,
+                                                 np_rr, rev);
+}
+
+// Jacobi's m: out[i] = 1 / (sum of row i's entries with col == i). Rows may
+// be unsorted and hold duplicates (the SpMV adds duplicates, so the diagonal
+// sums them, in entry order). One thread per row: setup only, once per
+// matrix, and rows are short; a row too long for that costs one slow thread,
+// not a wrong value. bad[0] counts the rows whose diagonal is missing, not
+// positive or not finite, bad[1] keeps the lowest such row.
+template <typename T> __device__ __forceinline__ bool pc_ok(T d) {
+  return d > T(0) && d <= std::numeric_limits<T>::max();  // false for NaN
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_diag_inv(int64_t n, const int *__restrict__ rowptr,
+                                                     const int *__restrict__ col,
+                                                     const T *__restrict__ val,
+                                                     T *__restrict__ out,
+                                                     unsigned long long *bad) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    T d = T(0);
+    bool found = false;
+    for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+      if (col[k] == i) {
+        d = d + val[k];
+        found = true;
+      }
+    }
+    out[i] = T(1) / d;
+    if (!found || !pc_ok(d)) {
+      atomicAdd(&bad[0], 1ull);
+      atomicMin(&bad[1], (unsigned long long)i);
+    }
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_diag_check(int64_t n, const T *__restrict__ m,
+                                                       unsigned long long *bad) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    if (!pc_ok(m[i])) {
+      atomicAdd(&bad[0], 1ull);
+      atomicMin(&bad[1], (unsigned long long)i);
+    }
+  }
+}
+
 // *dst = sum of part[0..np) in sum_parts order (partitioned runs: the local
 // dot before its RCCL all-reduce)
 template <typename T>
@@ -5482,6 +5906,68 @@ hipError_t Launch<T>::flush_defer(int64_t n, T *x, T *const P[4], CgScalars<T> *
   if (e != hipSuccess) return e;
   CGX_GGL(k_mark_defer<T>, dim3(1), dim3(1), 0, s, st);
   return hipGetLastError();
+}
+// ---- diagonal preconditioning: the grids of the kernels they mirror
+template <typename T>
+hipError_t Launch<T>::pc_init(int64_t n, const T *r, const T *m, T *p, CgScalars<T> *st,
+                              RedWs<T> *ws, hipStream_t s) {
+  CGX_LAUNCH(k_pc_init<T>, grid_elems(n, kGridUpdateP), n, r, m, p, st, ws);
+}
+template <typename T>
+hipError_t Launch<T>::update_r_pc(int64_t n, T *r, const T *Ap, const T *m, CgScalars<T> *st,
+                                  int slot, RedWs<T> *ws, hipStream_t s, int np_pap, int rev,
+                                  bool m_nt) {
+  if (np_pap < 1) return hipErrorInvalidValue;
+  const int g = grid_elems(n, kGridUpdateR);
+#define CGX_URPC(MNT, KP)                                                                 \
+  CGX_LAUNCH((k_update_r_pc<T, MNT, KP>), g, n, r, Ap, m, st, slot, ws, np_pap, rev)
+  if (np_pap <= 4 * kBlock) {
+    if (m_nt) CGX_URPC(true, 4);
+    CGX_URPC(false, 4);
+  }
+  if (np_pap <= 8 * kBlock) {
+    if (m_nt) CGX_URPC(true, 8);
+    CGX_URPC(false, 8);
+  }
+  if (m_nt) CGX_URPC(true, kPartsPerThread);
+  CGX_URPC(false, kPartsPerThread);
+#undef CGX_URPC
+}
+template <typename T>
+hipError_t Launch<T>::update_xp_pc(int64_t n, T *x, T *p, const T *r, const T *m,
+                                   CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr,
+                                   hipStream_t s, int rev, bool m_nt) {
+  if (np_rr < 1) return hipErrorInvalidValue;
+  if (m_nt)
+    CGX_LAUNCH((k_update_xp_pc<T, true>), grid_elems(n, kGridUpdateP), n, x, p, r, m, st, slot, ws,
+               np_rr, rev);
+  CGX_LAUNCH((k_update_xp_pc<T, false>), grid_elems(n, kGridUpdateP), n, x, p, r, m, st, slot, ws,
+             np_rr, rev);
+}
+template <typename T>
+hipError_t Launch<T>::update_p_defer_pc(int64_t n, T *x, const T *p, T *pn, T *const P[4],
+                                        const T *r, const T *m, CgScalars<T> *st, int slot,
+                                        RedWs<T> *ws, int np_rr, hipStream_t s, int rev,
+                                        bool m_nt) {
+  if (np_rr < 1) return hipErrorInvalidValue;
+#define CGX_UPPC(FL, MNT)                                                                  \
+  CGX_LAUNCH((k_update_p_defer_pc<T, FL, MNT>), grid_elems(n, kGridUpdateP), n, x, p, pn,  \
+             (const T *)P[0], (const T *)P[1], (const T *)P[2], r, m, st, slot, ws, np_rr, rev)
+  if (slot == 3) {
+    if (m_nt) CGX_UPPC(true, true);
+    CGX_UPPC(true, false);
+  }
+  if (m_nt) CGX_UPPC(false, true);
+  CGX_UPPC(false, false);
+#undef CGX_UPPC
+}
+template <typename T>
+hipError_t Launch<T>::diag_inv(const CsrDev &A, T *out, unsigned long long *bad, hipStream_t s) {
+  CGX_LAUNCH(k_diag_inv<T>, elem_grid(A.n, 1), A.n, A.rowptr, A.col, (const T *)A.val, out, bad);
+}
+template <typename T>
+hipError_t Launch<T>::diag_check(int64_t n, const T *m, unsigned long long *bad, hipStream_t s) {
+  CGX_LAUNCH(k_diag_check<T>, elem_grid(n, 4), n, m, bad);
 }
 template <typename T>
 hipError_t Launch<T>::dot_acc(int64_t n, const T *x, const T *y, T *res, RedWs<T> *ws,

@@ -239,6 +239,13 @@ struct cgx_cg {
   long long coop_ticks = 0; // wall-clock ticks before an exchange spin gives up
   bool altdir = false;  // alternate the kernels' sweep directions (Infinity-Cache reuse)
   void *pk[3] = {nullptr, nullptr, nullptr};  // p buffers 1..3 of mode 3 (n + n_ghost)
+  int mode_req = 0;     // the mode cgx_cg_set_mode was asked for (0: auto)
+  // diagonal preconditioning (cgx_cg_set_precond): the kind, the m the
+  // kernels read (minv_own for Jacobi, else the caller's) and how they load it
+  int precond = CGX_PRECOND_NONE;
+  const void *minv = nullptr;
+  void *minv_own = nullptr;
+  bool minv_nt = false;  // $CGX_PCG_M_NT=1: m through non-temporal loads (A/B)
   void *st = nullptr;   // cgx::CgScalars<T>
   void *ws = nullptr;   // cgx::RedWs<T>
   const void *b = nullptr;

@@ -45,6 +45,14 @@ struct CgDeleter {
 }  // namespace detail
 
 /**
+ * Extension (not in the reference): diagonal preconditioning of solve(),
+ * cgx.h's CGX_PRECOND_* kinds. Jacobi: 1 / diag(A), built on the device from
+ * the matrix; Diagonal: a vector the caller supplies.
+ */
+enum class Preconditioner { None = CGX_PRECOND_NONE, Jacobi = CGX_PRECOND_JACOBI,
+                            Diagonal = CGX_PRECOND_DIAGONAL };
+
+/**
  * @class CG (CG.hpp:53-601)
  * Set matrix, right-hand side and optional initial guess, solve, extract.
  */
@@ -188,6 +196,27 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
   double finalResidualSquared() const { return _final_rxr; }
   /** cap the loop bodies (< 0: the reference cap N + 1) */
   void setMaxIterations(long long m) { _max_iterations = m; }
+  /**
+   * None or Jacobi for the following solves (modes 1 and 3 of cgx.h; the
+   * stop rule still tests the true r.r). Diagonal needs its vector: the
+   * overload below.
+   * @throw std::invalid_argument for Diagonal
+   */
+  void setPreconditioner(Preconditioner kind) {
+    if (kind == Preconditioner::Diagonal)
+      throw std::invalid_argument("Preconditioner::Diagonal needs its vector: "
+                                  "setPreconditioner(Vector &&)");
+    _precond = kind;
+    _minv = Vector(_queue);
+    if (_solver) apply_precond(_solver.get());
+  }
+  /** Diagonal: minv (N positive, finite values on the device) is moved in */
+  void setPreconditioner(Vector &&minv) {
+    _minv = std::forward<Vector>(minv);
+    _precond = Preconditioner::Diagonal;
+    if (_solver) apply_precond(_solver.get());
+  }
+  Preconditioner preconditioner() const { return _precond; }
 
  private:
   void executeQueue() {
@@ -211,8 +240,19 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
       check(cgx_cg_create(_queue.native(), sched, &c), "cgx_cg_create");
       _solver = std::shared_ptr<cgx_cg>(c, detail::CgDeleter());
       _solver_for = sched;
+      // the choice survives a setMatrix (Jacobi is rebuilt from the new matrix)
+      if (_precond != Preconditioner::None) apply_precond(c);
     }
     return _solver.get();
+  }
+
+  void apply_precond(cgx_cg *c) {
+    if (_precond == Preconditioner::Diagonal &&
+        static_cast<std::size_t>(_minv.N()) != static_cast<std::size_t>(A.N()))
+      throw std::invalid_argument("setPreconditioner: the diagonal's length is not N");
+    check(cgx_cg_set_precond(c, static_cast<int>(_precond),
+                             _precond == Preconditioner::Diagonal ? _minv.ptr() : nullptr),
+          "setPreconditioner");
   }
 
   asycl::queue _queue;
@@ -225,6 +265,8 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
   long long _iterations = 0;
   double _final_rxr = 0;
   long long _max_iterations = -1;
+  Preconditioner _precond = Preconditioner::None;
+  Vector _minv{_queue};
 };
 
 };  // namespace CGSolver

@@ -276,7 +276,10 @@ int cgx_cg_config(cgx_cg *cg, int poll_every, int use_graph);
  * rule, slot 3 adds the x flush launch (60 N + 2 x matrix bytes per body);
  * never auto (slower than mode 6 at 256^3).
  * The dots are double-length sums (round 6), so modes 1, 3, 4, 6 and 7 give
- * bit-identical x whatever their grids. */
+ * bit-identical x whatever their grids.
+ * With a preconditioner set (cgx_cg_set_precond) only modes 1 and 3 run:
+ * auto resolves to 3 whatever the matrix, and modes 2, 4, 5, 6 and 7 return
+ * CGX_EUNSUPPORTED. */
 int cgx_cg_set_mode(cgx_cg *cg, int mode);
 /* mode 5's launch shape: rows per thread, threads per workgroup (1024),
  * workgroups, and the form: 0 the register form (drained write-through
@@ -295,6 +298,35 @@ int cgx_cg_get_mode(cgx_cg *cg, int *mode);
 /* mode 4's fused SpMV grid and the SpMV's: where they are equal mode 4 is
  * bit-identical to mode 1, else equal to rounding (one dot's sum order) */
 int cgx_csr_fd_grid(cgx_csr *A, int *fd_grid, int *spmv_grid);
+
+/* ---- diagonal preconditioning (replaces nothing in the reference: CG.hpp's
+ * solve is unpreconditioned) ------------------------------------------------
+ * PCG with M^-1 = diag(m): z = m o r (element product, rounded) is never
+ * stored, it is formed where the kernels hold r. init: p = m o r, rz = r.z;
+ * body: alpha = rz / p.Ap, r -= alpha Ap, rr' = r.r and rz' = r.(m o r) in
+ * one sweep, x += alpha p, beta = rz' / rz, p = m o r + beta p. tol, the
+ * body count, cgx_cg_rxr and cgx_cg_solve's rxr_out keep their meaning: the
+ * stop rule tests the true r.r (Q5), not r.z. With m == 1 every value is the
+ * plain solver's, bit for bit. The init is two launches (the plain one, then
+ * p = m o r with rz), both under index 0 of cgx_cg_kernel_times.
+ * Modes 1 and 3 on a single device, f64 and f32, every SpMV format; mode 0
+ * (auto) resolves to 3 while a preconditioner is set. Modes 2, 4, 5, 6, 7
+ * and partitioned matrices return CGX_EUNSUPPORTED, from whichever of
+ * cgx_cg_set_mode and cgx_cg_set_precond comes second. */
+enum { CGX_PRECOND_NONE = 0, CGX_PRECOND_JACOBI = 1, CGX_PRECOND_DIAGONAL = 2 };
+/* d_out[i] = 1 / a_ii (entries with col == row summed). Blocking. CGX_EINVAL when a row has no
+ * diagonal entry or a_ii is not positive and finite (the message gives the count and the first row). */
+int cgx_csr_diag_inv(cgx_csr *A, void *d_out);
+/* kind NONE: d_minv ignored. JACOBI: the solver builds and owns 1/diag(A) (d_minv ignored).
+ * DIAGONAL: d_minv = n caller-owned device values, positive and finite (checked, blocking),
+ * 16-byte aligned (cgx_alloc's are), alive until replaced or the solver is destroyed.
+ * Allowed between solves: it ends the current one (cgx_cg_run and cgx_cg_rxr need a new
+ * cgx_cg_begin, where it takes effect) and drops the captured graphs. On an error the
+ * solver keeps the preconditioner it had. */
+int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv);
+int cgx_cg_get_precond(cgx_cg *cg, int *kind);
+/* r.z after the last body (blocking); CGX_ESTATE without a preconditioner */
+int cgx_cg_rz(cgx_cg *cg, double *rz);
 
 /* CG::accuracy (CG.hpp:463-515): blocking; |sum (b-Ax)^2 / sum x^2|. */
 int cgx_accuracy(cgx_ctx *ctx, cgx_csr *A, const void *d_b, const void *d_x,
