@@ -74,6 +74,7 @@ _SIGS = {
     "cgx_csr_templates": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i64)]),
     "cgx_csr_lean_info": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32),
                                  C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "cgx_csr_lean_ring": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "cgx_csr_autotune_record": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32),
                                        C.POINTER(C.c_float), _i32, C.POINTER(_i32)]),
     "cgx_csr_setup_times": (_i32, [_vp, C.POINTER(_dbl), _i32, C.POINTER(_i32)]),

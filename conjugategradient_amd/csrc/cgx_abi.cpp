@@ -383,7 +383,7 @@ template <typename T> int enqueue_iter_defer(cgx_cg *cg, int slot) {
       return rc;
     return timed(cg, 3, s, [&] {
       return Launch<T>::update_p_defer(cg->n, x, p, pn, P, r, st, slot, ws,
-                                       lean_updr_parts(A->dev), s, par, nullptr);
+                                       A->dev.vl_grid, s, par, nullptr);
     });
   }
   if ((rc = enqueue_spmv_dot<T>(cg, p, slot, par, &npp))) return rc;
@@ -2386,6 +2386,14 @@ extern "C" int cgx_csr_lean_info(cgx_csr *A, int *classes, int64_t *slices, int 
   return CGX_OK;
 }
 
+extern "C" int cgx_csr_lean_ring(cgx_csr *A, int *tile, int *ring) {
+  CGX_REQUIRE(A && tile && ring, CGX_EINVAL, "NULL argument");
+  const bool whole = !A->dist && vl_whole(A->dev);
+  *tile = whole && lean_tile_ok(A->dev) ? 1 : 0;
+  *ring = whole && lean_ring_ok(A->dev) ? 1 : 0;
+  return CGX_OK;
+}
+
 extern "C" int cgx_csr_autotune_record(cgx_csr *A, int *variants, int *kinds, float *us,
                                        int cap, int *count) {
   CGX_REQUIRE(A && count && cap >= 0, CGX_EINVAL, "bad argument");
@@ -3176,7 +3184,15 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
     // the whole-matrix lean walk between fd_auto's two bounds (256^3):
     // mode 6, Ap recomputed by a second walk instead of stored — 5,207-5,214
     // against 4,920-4,944 it/s in mode 3 (profiles/r6h_mode6_ab.log)
-    if (mode == 3 && !cg->A->dist && vl_whole(cg->A->dev)) mode = 6;
+    if (mode == 3 && !cg->A->dist && vl_whole(cg->A->dev)) {
+      mode = 6;
+      // where mode 7's first kernel runs the ring walk (f64): p_k formed in
+      // that walk, 60 N bytes per body against 66 N — 5,643-5,754 against
+      // 5,286-5,315 it/s in mode 6 at 256^3, 6 interleaved runs each
+      // (profiles/ring_ab.log; 256 x 128 x 256: 9,879 against 8,702). With
+      // the per-wave tile walk mode 7 stays behind mode 6 (4,827 it/s)
+      if (cg->dtype == CGX_F64 && lean_ring_ok(cg->A->dev)) mode = 7;
+    }
   }
   const bool f = mode == 2, d = mode == 3 || mode == 6, fd = mode == 4 || mode == 7, c = mode == 5;
   const bool rc6 = mode == 6 || mode == 7;

@@ -2777,30 +2777,6 @@ __global__ __launch_bounds__(kBlock) void k_spmv_lean_updr(CsrArgs A, const T *_
   store_part(ws->rr_part, blockIdx.x, e.acc, sm.red);
 }
 
-// The tile walk's prefetch of an epilogue's own rows: none by default;
-// EpiUpdRT's r pairs come with the plane's outside pairs, two steps early
-struct NoPre {};
-template <class Epi> struct EpiPre {
-  using type = NoPre;
-  __device__ __forceinline__ static NoPre fetch(const Epi &, int) { return NoPre{}; }
-  __device__ __forceinline__ static void take(Epi &, const NoPre &) {}
-};
-// Mode 6's kernel 2 in the tile walk: EpiUpdR with r's pair prefetched
-// (pre2c loads nothing; the generic slices' pre / pre2 load as EpiUpdR)
-template <typename T> struct EpiUpdRT : EpiUpdR<T> {
-  __device__ __forceinline__ void pre2c(int, int, T, T) {}
-};
-template <typename T> struct EpiPre<EpiUpdRT<T>> {
-  using type = typename PairOf<T>::V;
-  __device__ __forceinline__ static type fetch(const EpiUpdRT<T> &e, int r0) {
-    return *reinterpret_cast<const type *>(e.r + r0);
-  }
-  __device__ __forceinline__ static void take(EpiUpdRT<T> &e, const type &v) {
-    e.rv = v.x;
-    e.rv1 = v.y;
-  }
-};
-
 // Lane l's value of v for every lane (l uniform)
 template <typename T> __device__ __forceinline__ T lane_bcast(T v, int l);
 template <> __device__ __forceinline__ double lane_bcast(double v, int l) {
@@ -2849,12 +2825,10 @@ __device__ __forceinline__ void spmv_lean_tile(const CsrArgs &A, const Gather &x
   struct CSlot {
     Raw c[Y];  // the plane's center pairs (formed in place the step before their first use)
   };
-  using Pre = typename EpiPre<Epi>::type;  // the epilogue's own rows (EpiUpdRT: r's pairs)
   struct ESlot {  // (two slots: plane i's, plane i + 1's)
     Raw em[NE];   // -a pairs of slices 0 .. NE - 1 (outside the tile)
     Raw ep[NE];   // +a pairs of slices Y - NE .. Y - 1
     Raw1 e;       // lane 0: row fr0 - 1; lane 63: row fr0 + 128 Y (the tile's x-line edges)
-    Pre pre[Y];
   };
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2912,8 +2886,6 @@ __device__ __forceinline__ void spmv_lean_tile(const CsrArgs &A, const Gather &x
     const int elo = fr0 > 0 ? fr0 - 1 : 0;
     const int ehi = fr0 + Y * 2 * kSellRows < nxi ? fr0 + Y * 2 * kSellRows : nxi - 1;
     sl.e = x.raw1(lane == 0 ? elo : lane == 63 ? ehi : fr0 + 2 * lane);
-#pragma unroll
-    for (int k = 0; k < Y; ++k) sl.pre[k] = EpiPre<Epi>::fetch(epi, fr0 + k * 2 * kSellRows + 2 * lane);
   };
   // plane i's sums: behind / center / ahead in walk order (-D / +D swap in
   // the reversed sweep)
@@ -2954,7 +2926,6 @@ __device__ __forceinline__ void spmv_lean_tile(const CsrArgs &A, const Gather &x
       const T hi_e = tab[c].phi ? ehi : -__builtin_copysign(T(0), v[4]);
       const T left = wave_shr1(ct.y, lo_e), right = wave_shl1(ct.x, hi_e);
       epi.pre2c(r0, r0 + 1, ct.x, ct.y);
-      EpiPre<Epi>::take(epi, se.pre[k]);
       T a0 = T(0), a1 = T(0);
       if (pres == 15) {  // every slot present (the interior): no select
         a0 = a0 + v[0] * gmD.x;
@@ -3067,41 +3038,6 @@ __global__ __launch_bounds__(kBlock, kTileW) void k_spmv_lean_dot_tile(CsrArgs A
   store_part(ws->pap_part, blockIdx.x, e.acc, sm.red);
 }
 
-// Mode 6's kernel 2 in the tile walk (lean_tile_ok): k_spmv_lean_updr's
-// values, r's pairs prefetched with the planes
-template <typename T>
-__global__ __launch_bounds__(kBlock, kTileW) void k_spmv_lean_updr_tile(CsrArgs A,
-                                                                        const T *__restrict__ p,
-                                                                        T *__restrict__ r,
-                                                                        CgScalars<T> *st, int slot,
-                                                                        RedWs<T> *ws, int np_pap) {
-  if (!st->active[slot]) return;
-  __shared__ SellLds<T> sm;
-  const T pAp = sum_parts(ws->pap_part, np_pap, sm.red);
-  const T alpha = st->rxr[slot] / pAp;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    st->pAp[slot] = pAp;
-    st->alpha[slot] = alpha;
-    st->skip[slot] = 0;
-  }
-  const T *vd = static_cast<const T *>(A.svdict);
-  const unsigned long long *vt = A.vct;
-  if (A.vl_lds) {
-    lean_lds(A, sm);
-    vd = sm.vdict;
-    vt = sm.vt;
-  }
-  EpiUpdRT<T> e;
-  e.r = r;
-  e.alpha = alpha;
-  e.acc = Dd<T>(T(0));
-  if (A.rev)
-    spmv_lean_tile<T, kTileY, kTileM, kTileDist, true>(A, GatherX<T>{p}, e, vd, vt, kTileZ);
-  else
-    spmv_lean_tile<T, kTileY, kTileM, kTileDist, false>(A, GatherX<T>{p}, e, vd, vt, kTileZ);
-  store_part(ws->rr_part, blockIdx.x, e.acc, sm.red);
-}
-
 // Mode 7 (cgx_abi.cpp enqueue_iter_fdefer), kernel 1 of 2 (3 in slot 3):
 // k_spmv_fd_lean's preamble (beta from body k-1's r.r partials, the records,
 // slot 0 opening a group) and its p_k = r + beta p_{k-1} into P[s], in the
@@ -3115,7 +3051,7 @@ __global__ __launch_bounds__(kBlock, kTileW) void k_spmv_lean_updr_tile(CsrArgs 
 // 111 with a spill; profiles/r6t_*)
 constexpr int kFdZ = 1, kFdDist = 1, kFdW = 4 * kFdZ / kTileY;
 template <typename T>
-__global__ __launch_bounds__(kBlock, kFdW) void k_spmv_fd_dot_tile(
+__global__ __launch_bounds__(kBlock, kFdW) void k_spmv_fd_dot_wave(
     CsrArgs A, const T *__restrict__ r, const T *__restrict__ pold, T *__restrict__ pc,
     CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr) {
   __shared__ SellLds<T> sm;
@@ -3157,6 +3093,352 @@ __global__ __launch_bounds__(kBlock, kFdW) void k_spmv_fd_dot_tile(
   else
     spmv_lean_tile<T, kTileY, kTileM, kFdDist, false>(A, g, e, vd, vt, kFdZ);
   store_part(ws->pap_part, blockIdx.x, e.acc, sm.red);
+}
+
+// Ring form of the tile walk (lean_ring_ok; DESIGN.md §5 "The ring walk"): a
+// workgroup of W waves owns W consecutive x-lines of a plane (a wave one
+// line: Y = M slices), and a plane's formed center pairs are shared through
+// LDS instead of every wave loading its +-a neighbours' lines again. A wave
+// keeps the tile walk's center ring in registers (-D / center / +D are its
+// own centers, loaded DIST + 2 planes ahead); each step it writes plane i's
+// formed centers to pub[i mod 2], the W waves together write the two halo
+// lines (y0 - 1 and y0 + W: 2 Y slices, 64 / HS pairs per wave, loaded two
+// steps ahead), one LDS-only barrier, and the sums take the +-a pairs and the
+// x-line edge values from pub. The buffer written at step i + 1 was last read
+// in step i - 1's sums, which every wave left before step i's barrier. The
+// trip count comes from ib, ie alone: every wave executes the same barriers.
+// Per row the same products in the same order as spmv_lean_tile: Ap bit for
+// bit. Loads per line of the plane: (W + 2) / W instead of 3.
+template <typename T, int W, int Y> struct RingLds {
+  typename PairU<T>::V pub[2][W + 2][Y][64];
+  T red[2 * W + 2];
+};
+template <typename T, int W>
+__device__ __forceinline__ Dd<T> ring_block_sum_dd(Dd<T> v, T *lds) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  v = wave_sum_dd(v);
+  if (lane == 0) {
+    lds[2 * w] = v.hi;
+    lds[2 * w + 1] = v.lo;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    v = Dd<T>(lds[0], lds[1]);
+#pragma unroll
+    for (int k = 1; k < W; ++k) v += Dd<T>(lds[2 * k], lds[2 * k + 1]);
+  }
+  __syncthreads();
+  return v;
+}
+// sum_parts for a workgroup of W waves (thread t: t, t + 64 W, ...; every
+// workgroup the identical value)
+template <typename T, int W>
+__device__ __forceinline__ T ring_sum_parts(const T *__restrict__ part, int np, T *lds) {
+  Dd<T> v(T(0));
+  for (int i = threadIdx.x; i < np; i += 64 * W) v += load_part(part, i);
+  v = ring_block_sum_dd<T, W>(v, lds);
+  if (threadIdx.x == 0) {
+    lds[2 * W] = v.hi;
+    lds[2 * W + 1] = v.lo;
+  }
+  __syncthreads();
+  const Dd<T> s(lds[2 * W], lds[2 * W + 1]);
+  __syncthreads();  // (lds is written again by the next reduction)
+  return s.value();
+}
+template <typename T, int W>
+__device__ __forceinline__ void ring_store_part(T *part, int i, Dd<T> v, T *lds) {
+  v = ring_block_sum_dd<T, W>(v, lds);
+  if (threadIdx.x == 0) {
+    part[2 * i] = v.hi;
+    part[2 * i + 1] = v.lo;
+  }
+}
+template <typename T, int W>
+__device__ __forceinline__ void ring_lean_lds(const CsrArgs &A, SellLds<T> &sm) {
+  const T *__restrict__ src = static_cast<const T *>(A.svdict);
+  for (int i = threadIdx.x; i < kVcDict; i += 64 * W) sm.vdict[i] = src[i];
+  for (int i = threadIdx.x; i < A.nvt * 64; i += 64 * W) sm.vt[i] = A.vct[i];
+  __syncthreads();
+}
+
+template <typename T, int W, int Y, int M, int DIST, bool REV, class Epi, class Gather>
+__device__ __forceinline__ void spmv_lean_ring(const CsrArgs &A, const Gather &x, Epi &epi,
+                                               const T *__restrict__ vd,
+                                               const unsigned long long *vt, int zs,
+                                               RingLds<T, W, Y> &rl) {
+  static_assert(Y == M, "a wave owns one x-line: its +-a pairs are the next waves' centers");
+  static_assert(W % (2 * Y) == 0 && 64 % (W / (2 * Y)) == 0, "halo slices split over the waves");
+  constexpr int VG = 8192 | 32768 | 262144 | 524288 | kVT | 2;  // the generic slices' form
+  constexpr int NRC = DIST + 3;               // center ring: planes i - 1 .. i + 1 + DIST
+  constexpr int U = NRC % 2 ? 2 * NRC : NRC;  // unroll (even: pub's parity is u mod 2)
+  constexpr int HS = W / (2 * Y);             // waves per halo slice
+  constexpr int HL = 64 / HS;                 // pairs of a halo slice per wave
+  using PV = decltype(x.pair_b(0u));
+  using Raw = typename Gather::Raw;
+  auto to_raw = [](const PV &v) {
+    Raw w;
+    if constexpr (std::is_same<Raw, PV>::value) w = v;
+    else w.a = v;
+    return w;
+  };
+  auto formed = [](const Raw &w) -> PV {
+    if constexpr (std::is_same<Raw, PV>::value) return w;
+    else return w.a;
+  };
+  struct CSlot {
+    Raw c[Y];
+  };
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // workgroup b: XCD group g = b mod 8, lines t W .. t W + W - 1 of the plane,
+  // part zp of the group's planes
+  const int b = (int)blockIdx.x, g = b & 7;
+  const int tpg = (int)gridDim.x / (8 * zs);  // workgroups per plane
+  const int step = tpg * W * Y;               // walk positions per plane (the layout's)
+  const int t = (b >> 3) % tpg, zp = (b >> 3) / tpg;
+  const int qw = t * W * Y, q0 = qw + wid * Y;
+  const int nsl = (int)A.nsl;
+  const int lo = (int)(((int64_t)nsl * g) >> 3), end = (int)(((int64_t)nsl * (g + 1)) >> 3);
+  const int J = (end - lo) / step;
+  const int ib = zp * J / zs, ie = (zp + 1) * J / zs;  // the workgroup's walk indices
+  const int nw = A.vl_nst >> 2;
+  const auto *tab = (const __attribute__((address_space(4))) VlClass *)A.vl_tab;
+  const int a = A.vl_a, nxi = (int)A.nx;
+  const unsigned oa = (unsigned)a * (unsigned)sizeof(T);
+  unsigned cw[Y];
+#pragma unroll
+  for (int k = 0; k < Y; ++k) {
+    const unsigned *__restrict__ row = reinterpret_cast<const unsigned *>(
+        A.vl_cls + (int64_t)(g * step + q0 + k) * A.vl_nst);
+    const unsigned w = row[lane < nw ? lane : 0];
+    cw[k] = lane < nw ? w : ~0u;
+  }
+  // this wave's share of the halo lines: slice hk of the line below (hside 0)
+  // or above (1) the workgroup's, pairs hp0 .. hp0 + HL - 1 (the lanes of a
+  // wave repeat them HS times: one load instruction per wave whatever HS)
+  const int hside = (wid / HS) / Y, hk = (wid / HS) % Y;
+  const int hp = (wid % HS) * HL + (lane % HL);
+  // the first row of walk index i's plane at walk position q (spmv_lean_tile's
+  // first_row: indices -1 and J clamp to an in-bounds plane at the matrix's ends)
+  auto first_row = [&](int i, int q, int n) {
+    const int j = REV ? J - 1 - i : i;
+    const int s0 = lo + q + j * step;
+    return ((s0 < 0 || s0 + n > nsl) ? lo + q : s0) * (2 * kSellRows);
+  };
+  auto load_c = [&](int i, CSlot &sl) {
+    const int fr0 = first_row(i, q0, Y);
+#pragma unroll
+    for (int k = 0; k < Y; ++k)
+      sl.c[k] = x.raw_b((unsigned)(fr0 + k * 2 * kSellRows + 2 * lane) * (unsigned)sizeof(T));
+  };
+  // (the addresses spmv_lean_tile's em / ep take for the workgroup's first and
+  // last line: the line a rows away, or the line itself where that is outside
+  // the matrix and the class marks the pair absent)
+  auto load_h = [&](int i) -> Raw {
+    const int frw = first_row(i, qw, W * Y);
+    const int fr = frw + ((hside ? (W - 1) * Y : 0) + hk) * 2 * kSellRows;
+    const unsigned rb = (unsigned)(fr + 2 * hp) * (unsigned)sizeof(T);
+    const bool in = hside ? (a > 0 && fr + 2 * kSellRows + a <= nxi) : (a > 0 && fr >= a);
+    return x.raw_b(hside ? rb + (in ? oa : 0u) : rb - (in ? oa : 0u));
+  };
+  auto form_c = [&](CSlot &sl) {
+#pragma unroll
+    for (int k = 0; k < Y; ++k) sl.c[k] = to_raw(x.form(sl.c[k]));
+  };
+  // plane i's formed centers and this wave's share of its halo lines into pub[par]
+  auto publish = [&](int par, const CSlot &sc, const Raw &h) {
+#pragma unroll
+    for (int k = 0; k < Y; ++k) rl.pub[par][wid + 1][k][lane] = formed(sc.c[k]);
+    rl.pub[par][hside ? W + 1 : 0][hk][hp] = x.form(h);  // (HS lanes store the same pair)
+  };
+  auto sum = [&](int i, int par, const CSlot &sb, const CSlot &sc, const CSlot &sa) {
+    const int j = REV ? J - 1 - i : i;
+    const int s0 = lo + q0 + j * step;
+    const int jb = j >> 2, jsh = 8 * (j & 3);
+#pragma unroll
+    for (int k = 0; k < Y; ++k) {
+      const unsigned word = (unsigned)__builtin_amdgcn_readlane((int)cw[k], jb);
+      const int c = (int)((word >> jsh) & 0xffu);
+      const int si = s0 + k;
+      if (c >= 0xfe) continue;  // the generic slices run after the walk
+      const int fr = si * (2 * kSellRows);
+      const int r0 = fr + 2 * lane;
+      const PV ct = formed(sc.c[k]);
+      const PV gmD = formed(REV ? sa.c[k] : sb.c[k]);
+      const PV gpD = formed(REV ? sb.c[k] : sa.c[k]);
+      const PV gma = rl.pub[par][wid][k][lane];
+      const PV gpa = rl.pub[par][wid + 2][k][lane];
+      const int pres = tab[c].pres;
+      T v[7];
+#pragma unroll
+      for (int q = 0; q < 7; ++q) v[q] = T(tab[c].v[q]);
+      // rows fr0 - 1 and fr0 + 128 Y: the last pair of the line below, the
+      // first of the line above
+      const T elo = k == 0 ? T(rl.pub[par][wid][Y - 1][63].y)
+                           : lane_bcast(formed(sc.c[k > 0 ? k - 1 : 0]).y, 63);
+      const T ehi = k == Y - 1 ? T(rl.pub[par][wid + 2][0][0].x)
+                               : lane_bcast(formed(sc.c[k + 1 < Y ? k + 1 : 0]).x, 0);
+      const T lo_e = tab[c].plo ? elo : -__builtin_copysign(T(0), v[2]);
+      const T hi_e = tab[c].phi ? ehi : -__builtin_copysign(T(0), v[4]);
+      const T left = wave_shr1(ct.y, lo_e), right = wave_shl1(ct.x, hi_e);
+      epi.pre2c(r0, r0 + 1, ct.x, ct.y);
+      T a0 = T(0), a1 = T(0);
+      if (pres == 15) {  // every slot present (the interior): no select
+        a0 = a0 + v[0] * gmD.x;
+        a1 = a1 + v[0] * gmD.y;
+        a0 = a0 + v[1] * gma.x;
+        a1 = a1 + v[1] * gma.y;
+        a0 = a0 + v[2] * left;
+        a1 = a1 + v[2] * ct.x;
+        a0 = a0 + v[3] * ct.x;
+        a1 = a1 + v[3] * ct.y;
+        a0 = a0 + v[4] * ct.y;
+        a1 = a1 + v[4] * right;
+        a0 = a0 + v[5] * gpa.x;
+        a1 = a1 + v[5] * gpa.y;
+        a0 = a0 + v[6] * gpD.x;
+        a1 = a1 + v[6] * gpD.y;
+      } else {
+        if (pres & 1) {
+          a0 = a0 + v[0] * gmD.x;
+          a1 = a1 + v[0] * gmD.y;
+        }
+        if (pres & 2) {
+          a0 = a0 + v[1] * gma.x;
+          a1 = a1 + v[1] * gma.y;
+        }
+        a0 = a0 + v[2] * left;
+        a1 = a1 + v[2] * ct.x;
+        a0 = a0 + v[3] * ct.x;
+        a1 = a1 + v[3] * ct.y;
+        a0 = a0 + v[4] * ct.y;
+        a1 = a1 + v[4] * right;
+        if (pres & 4) {
+          a0 = a0 + v[5] * gpa.x;
+          a1 = a1 + v[5] * gpa.y;
+        }
+        if (pres & 8) {
+          a0 = a0 + v[6] * gpD.x;
+          a1 = a1 + v[6] * gpD.y;
+        }
+      }
+      epi.row2(r0, a0, a1, true, true);
+    }
+  };
+  CSlot cr[NRC];
+  Raw hr[2];
+  // prologue: walk indices ib - 1 .. ib + DIST + 1 in center slots 0 .. NRC - 1,
+  // ib and ib + 1's halo shares
+  hr[0] = load_h(ib);
+  hr[1] = load_h(ib + 1);
+#pragma unroll
+  for (int u = 0; u < NRC; ++u) load_c(ib + u - 1, cr[u]);
+  form_c(cr[0]);
+  form_c(cr[1]);
+  // step i (u = i - ib): plane i (center slot u + 1, formed the step before)
+  // and halo slot u mod 2 published, the barrier, plane i + 1 formed, the sums,
+  // then plane i + 2's halo share and plane i + 2 + DIST's centers loaded. The
+  // loads are never skipped (past the walk's end they re-read an in-bounds
+  // plane): every path issues the same loads
+  for (int i0 = ib; i0 < ie; i0 += U) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = i0 + u;
+      if (i < ie) {  // (uniform over the workgroup)
+        publish(u % 2, cr[(u + 1) % NRC], hr[u % 2]);
+        lds_barrier();
+      }
+      form_c(cr[(u + 2) % NRC]);
+      if (i < ie) sum(i, u % 2, cr[u % NRC], cr[(u + 1) % NRC], cr[(u + 2) % NRC]);
+      hr[u % 2] = load_h(i + 2);
+      load_c(i + 2 + DIST, cr[u % NRC]);
+    }
+  }
+  // the slices of other patterns (class 0xff), per wave, no barrier
+  for (int i = ib; i < ie; ++i) {
+    const int j = REV ? J - 1 - i : i;
+#pragma unroll
+    for (int k = 0; k < Y; ++k) {
+      const unsigned word = (unsigned)__builtin_amdgcn_readlane((int)cw[k], j >> 2);
+      if (((word >> (8 * (j & 3))) & 0xffu) == 0xff)
+        sellpv_slice2<T, VG, Epi, Gather>(A, x, epi, vd, lo + q0 + j * step + k, vt);
+    }
+  }
+}
+
+// GatherP with p_{k-1}'s center pairs read non-temporally (each line is read
+// once here; the slot-3 flush reads it again, up to seven kernels later)
+template <typename T> struct GatherPN : GatherP<T> {
+  using typename GatherP<T>::Raw;
+  __device__ __forceinline__ Raw raw_b(unsigned b) const {
+    using U = typename PairU<T>::V;
+    return Raw{*reinterpret_cast<const U *>(reinterpret_cast<const char *>(this->r) + b),
+               __builtin_nontemporal_load(
+                   reinterpret_cast<const U *>(reinterpret_cast<const char *>(this->pp) + b))};
+  }
+};
+// Mode 7's kernel 1 in the ring walk (lean_ring_ok): k_spmv_fd_dot_wave's
+// preamble and values. kFdRingW waves per workgroup, kFdRingZ parts of each
+// group's planes, centers kFdRingDist + 2 planes ahead, four waves per SIMD
+// (128 VGPRs, 12 bytes of scratch; 46 KB of LDS, two workgroups per CU).
+// Measured at 256^3, us in the loop against the per-wave form's 101.9
+// (profiles/ring_tune.log): W 8 Z 2 DIST 1 75.8-77.9; W 8 Z 1 77.5-79.3;
+// W 8 Z 2 DIST 0 81.1; W 8 Z 2 DIST 2 90.4; W 8 Z 1 DIST 2 89.4; W 4 Z 2
+// 78.2; W 16 Z 2 77.8. With p_{k-1}'s centers read non-temporally (GatherPN)
+// the kernel itself ran 81.4 but kernel 2 then 65.5 instead of 72-75 (it
+// finds more of p_k in the Infinity Cache) and the body won: 5,739 against
+// 5,577 it/s, medians of 5 interleaved runs (profiles/ring_ab.log).
+constexpr int kFdRingW = 8, kFdRingZ = 2, kFdRingDist = 1;
+template <typename T>
+__global__ __launch_bounds__(64 * kFdRingW, 4) void k_spmv_fd_dot_tile(
+    CsrArgs A, const T *__restrict__ r, const T *__restrict__ pold, T *__restrict__ pc,
+    CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr) {
+  __shared__ SellLds<T> sm;
+  __shared__ RingLds<T, kFdRingW, kTileY> rl;
+  const int prev = (slot + 3) & 3;
+  const long long bodies = st->bodies;
+  const bool act = st->active[slot] != 0;
+  if (slot == 0 && blockIdx.x == 0 && threadIdx.x == 0)
+    for (int t = 0; t < 4; ++t) st->ran[t] = 0;
+  if (!act) {
+    if (blockIdx.x == 0 && bodies > 0 && (int)(bodies & 3) == slot) {
+      const T rr = ring_sum_parts<T, kFdRingW>(ws->rr_part, np_rr, rl.red);
+      if (threadIdx.x == 0) {
+        st->rr[prev] = rr;
+        st->rxr[slot] = rr;
+      }
+    }
+    return;
+  }
+  T beta = T(0);
+  if (bodies > 0) {
+    const T rr = ring_sum_parts<T, kFdRingW>(ws->rr_part, np_rr, rl.red);
+    beta = rr / st->rxr[prev];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      st->rr[prev] = rr;  // the record
+      st->rxr[slot] = rr;
+    }
+  }
+  const T *vd = static_cast<const T *>(A.svdict);
+  const unsigned long long *vt = A.vct;
+  if (A.vl_lds) {
+    ring_lean_lds<T, kFdRingW>(A, sm);
+    vd = sm.vdict;
+    vt = sm.vt;
+  }
+  const GatherP<T> g{r, pold, beta};
+  EpiFDDot<T> e{pc, g, T(0), T(0), T(0)};  // (g: the generic slices' own rows)
+  GatherPN<T> gn;
+  gn.r = r;
+  gn.pp = pold;
+  gn.beta = beta;
+  if (A.rev)
+    spmv_lean_ring<T, kFdRingW, kTileY, kTileM, kFdRingDist, true>(A, gn, e, vd, vt, kFdRingZ, rl);
+  else
+    spmv_lean_ring<T, kFdRingW, kTileY, kTileM, kFdRingDist, false>(A, gn, e, vd, vt, kFdRingZ,
+                                                                    rl);
+  ring_store_part<T, kFdRingW>(ws->pap_part, blockIdx.x, e.acc, rl.red);
 }
 
 // Mode 7, kernel 2: k_spmv_lean_updr on the stored p_k with update_r's stop
@@ -5341,22 +5623,22 @@ bool lean_tile_ok(const CsrDev &A) {
   return (A.nsl / 8) / step >= 8 * kTileZ;
 }
 // p.Ap partials of mode 6's kernel 1: one per workgroup of its launch
+// The ring walk (spmv_lean_ring: mode 7's kernel 1) takes the tile walk's
+// layout when a plane's x-lines divide into whole workgroups of kFdRingW
+// waves and every part of a group has its 8 planes; $CGX_LEAN_RING=0 (read
+// at each call: an A/B within one process) keeps the per-wave tile walk
+bool lean_ring_ok(const CsrDev &A) {
+  const char *e = getenv("CGX_LEAN_RING");
+  if ((e && !atoi(e)) || !lean_tile_ok(A)) return false;
+  const int step = A.vl_grid / 2;  // walk positions of a plane (lean_tile_ok)
+  return (step / kTileY) % kFdRingW == 0 && (A.nsl / 8) / step >= 8 * kFdRingZ;
+}
 int lean_dot_parts(const CsrDev &A) {
   return lean_tile_ok(A) ? A.vl_grid / kTileY * kTileZ : A.vl_grid;  // 8 step kTileZ / (4 Y)
 }
-int fd_dot_parts(const CsrDev &A) { return A.vl_grid / kTileY * kFdZ; }
-// mode 6's kernel 2 in the tile form ($CGX_LEAN_TILE_UPDR=1; with r's pairs
-// prefetched it ran 74.4 against 68.6 us at 256^3, profiles/r6t_*: off by
-// default), and its r.r partials
-bool lean_updr_tile(const CsrDev &A) {
-  static const int env = [] {
-    const char *e = getenv("CGX_LEAN_TILE_UPDR");
-    return e ? atoi(e) : 0;
-  }();
-  return env && lean_tile_ok(A);
-}
-int lean_updr_parts(const CsrDev &A) {
-  return lean_updr_tile(A) ? A.vl_grid / kTileY * kTileZ : A.vl_grid;
+int fd_dot_parts(const CsrDev &A) {
+  if (lean_ring_ok(A)) return A.vl_grid / 2 / kTileY / kFdRingW * 8 * kFdRingZ;
+  return A.vl_grid / kTileY * kFdZ;
 }
 template <typename T> int Launch<T>::lean_resident() {
   static std::mutex mu;
@@ -5416,7 +5698,12 @@ hipError_t Launch<T>::fd_dot_tile(const CsrDev &A, const T *r, const T *pold, T 
   if (!lean_tile_ok(A)) return hipErrorInvalidValue;
   CsrArgs a = args(A);
   a.rev = rev;
-  CGX_GGL(k_spmv_fd_dot_tile<T>, dim3(fd_dot_parts(A)), dim3(kBlock), 0, s, a, r, pold, pc, st,
+  if (lean_ring_ok(A)) {
+    CGX_GGL(k_spmv_fd_dot_tile<T>, dim3(fd_dot_parts(A)), dim3(64 * kFdRingW), 0, s, a, r, pold,
+            pc, st, slot, ws, np_rr);
+    return hipGetLastError();
+  }
+  CGX_GGL(k_spmv_fd_dot_wave<T>, dim3(fd_dot_parts(A)), dim3(kBlock), 0, s, a, r, pold, pc, st,
           slot, ws, np_rr);
   return hipGetLastError();
 }
@@ -5436,11 +5723,6 @@ hipError_t Launch<T>::lean_updr(const CsrDev &A, const T *p, T *r, CgScalars<T> 
   if (!vl_whole(A)) return hipErrorInvalidValue;
   CsrArgs a = args(A);
   a.rev = rev;
-  if (lean_updr_tile(A)) {
-    CGX_GGL(k_spmv_lean_updr_tile<T>, dim3(lean_updr_parts(A)), dim3(kBlock), 0, s, a, p, r, st,
-            slot, ws, lean_dot_parts(A));
-    return hipGetLastError();
-  }
   CGX_GGL(k_spmv_lean_updr<T>, dim3(A.vl_grid), dim3(kBlock), 0, s, a, p, r, st, slot, ws,
           lean_dot_parts(A));
   return hipGetLastError();

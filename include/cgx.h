@@ -135,6 +135,13 @@ int cgx_csr_templates(cgx_csr *csr, int *n_templates, int64_t *slices);
  * VectorOperations.hpp:438-466's SpMV. */
 int cgx_csr_lean_info(cgx_csr *csr, int *classes, int64_t *slices, int *grid, int *D, int *a,
                       int *chunked);
+/* Which form of the plane-per-step walk the recomputed-Ap modes take on this
+ * matrix: *tile = 1 when the tile walk applies (modes 6 and 7's first kernels:
+ * one wave per x-line, the planes it needs in flight ahead of its sums),
+ * *ring = 1 when mode 7's first kernel runs its ring form (a workgroup shares
+ * a plane's lines through LDS), which is also where auto resolves to mode 7
+ * for f64. Read at the call: $CGX_LEAN_RING=0 keeps the per-wave tile form. */
+int cgx_csr_lean_ring(cgx_csr *csr, int *tile, int *ring);
 /* The SpMV autotune's record of this matrix (cgx_csr_create /
  * cgx_csr_create_dist): every form it timed, how it was timed and its median
  * µs per launch over the interleaved rounds; *count = the record's length
@@ -273,8 +280,10 @@ int cgx_cg_config(cgx_cg *cg, int poll_every, int use_graph);
  * Mode 7 (single device, f64, a 3-D stencil whose lean layout takes the tile
  * walk): mode 4's body with no Ap vector — kernel 1 forms p_k into the p ring
  * and keeps p.Ap, kernel 2 walks A p_k again, updates r and runs the stop
- * rule, slot 3 adds the x flush launch (60 N + 2 x matrix bytes per body);
- * never auto (slower than mode 6 at 256^3).
+ * rule, slot 3 adds the x flush launch (60 N + 2 x matrix bytes per body).
+ * Auto takes 7 instead of 6 where kernel 1 runs the ring form of the tile
+ * walk (cgx_csr_lean_ring; 256^3: DESIGN.md §5) and 6 for the other
+ * whole-matrix lean walks between mode 4's two bounds.
  * The dots are double-length sums (round 6), so modes 1, 3, 4, 6 and 7 give
  * bit-identical x whatever their grids.
  * With a preconditioner set (cgx_cg_set_precond) only modes 1 and 3 run:
