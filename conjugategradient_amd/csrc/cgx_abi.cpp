@@ -300,6 +300,22 @@ int dist_dot(cgx_cg *cg, const T *part, int np, T *dst, int slot, int which) {
   return dist_allreduce_scalar(cg->ctx, dst, cg->dtype, 1, s);
 }
 
+// A preconditioned partitioned body's second all-reduce step: the local r.r
+// and r.z all-reduced together into st->rrz[2 slot..], one collective of two
+// values (the peer one-waiter form: one k_peer_allreduce2 launch, one tag;
+// host / RCCL: one finalize launch, then one all-reduce with count 2). The
+// plain body's r.r step, with the same number of launches and round trips.
+template <typename T> int dist_dot_pair(cgx_cg *cg, int np, int slot) {
+  hipStream_t s = cg->ctx->stream;
+  auto *st = (CgScalars<T> *)cg->st;
+  auto *ws = (RedWs<T> *)cg->ws;
+  T *dst = &st->rrz[2 * slot];
+  if (cg->A->peer.on)
+    return peer_allreduce2<T>(cg->A, ws->rr_part, ws->rz_part, np, dst, st, slot, s, 2);
+  CGX_HIP(Launch<T>::finalize2(ws->rr_part, ws->rz_part, np, dst, s));
+  return dist_allreduce_scalar(cg->ctx, dst, cg->dtype, 2, s);
+}
+
 // The device peer transport's two all-reduces of a body run inside the
 // kernels that consume them (update_r: p.Ap, the x/p update: r.r; every
 // workgroup polls the mailboxes, peerdev::world_sum) instead of as two
@@ -327,6 +343,20 @@ template <typename T> int enqueue_iter(cgx_cg *cg, int slot) {
   const PeerDev *far = fused_ar(cg);
   const bool sep = A->dist && !far;  // a separate all-reduce step per dot
   if ((rc = enqueue_spmv_dot<T>(cg, p, slot, par, &npp))) return rc;
+  if (cg->precond && A->dist) {
+    // partitioned: the plain partitioned body's steps, with
+    // the r.r all-reduce carrying r.z as its second value (tag base + 2)
+    const T *m = (const T *)cg->minv;
+    if (sep && (rc = dist_dot<T>(cg, ws->pap_part, npp, &st->pAp[slot], slot, 1))) return rc;
+    if ((rc = timed(cg, 2, s, [&] {
+           return Launch<T>::update_r_pc_dist(cg->n, r, Ap, m, st, slot, ws, s, npp, rpar, far);
+         })))
+      return rc;
+    if (sep && (rc = dist_dot_pair<T>(cg, npr, slot))) return rc;
+    return timed(cg, 3, s, [&] {
+      return Launch<T>::update_xp_pc_dist(cg->n, x, p, r, m, st, slot, ws, npr, s, par, far);
+    });
+  }
   if (cg->precond) {  // single device (cgx_cg_set_precond): the SpMV launch is the plain one
     const T *m = (const T *)cg->minv;
     if ((rc = timed(cg, 2, s, [&] {
@@ -387,6 +417,19 @@ template <typename T> int enqueue_iter_defer(cgx_cg *cg, int slot) {
     });
   }
   if ((rc = enqueue_spmv_dot<T>(cg, p, slot, par, &npp))) return rc;
+  if (cg->precond && A->dist) {  // partitioned: as enqueue_iter's
+    const T *m = (const T *)cg->minv;
+    if (sep && (rc = dist_dot<T>(cg, ws->pap_part, npp, &st->pAp[slot], slot, 1))) return rc;
+    if ((rc = timed(cg, 2, s, [&] {
+           return Launch<T>::update_r_pc_dist(cg->n, r, Ap, m, st, slot, ws, s, npp, rpar, far);
+         })))
+      return rc;
+    if (sep && (rc = dist_dot_pair<T>(cg, npr, slot))) return rc;
+    return timed(cg, 3, s, [&] {
+      return Launch<T>::update_p_defer_pc_dist(cg->n, x, p, pn, P, r, m, st, slot, ws, npr, s,
+                                               par, far);
+    });
+  }
   if (cg->precond) {  // single device (cgx_cg_set_precond): the SpMV launch is the plain one
     const T *m = (const T *)cg->minv;
     if ((rc = timed(cg, 2, s, [&] {
@@ -3266,26 +3309,82 @@ template <class F> int pc_scan(cgx_ctx *ctx, unsigned long long (&h)[2], F &&lau
   CGX_HIP(e);
   return CGX_OK;
 }
-}  // namespace
 
-extern "C" int cgx_csr_diag_inv(cgx_csr *A, void *d_out) {
-  CGX_REQUIRE(A && d_out, CGX_EINVAL, "NULL argument");
-  CGX_REQUIRE(!A->dist, CGX_EUNSUPPORTED,
-              "cgx_csr_diag_inv: a partitioned matrix (diagonal preconditioning runs on a single "
-              "device, modes 1 and 3)");
-  if (A->dev.n == 0) return CGX_OK;
+// A partitioned matrix: the ranks' verdicts on a scan agreed over the setup
+// transport, so that every rank returns the same code. Each rank brings its
+// scan's {count, lowest local index} and the status it reached on its own
+// (an argument error, a failed allocation or launch): the counts are summed,
+// the lowest GLOBAL index is kept, and a status other than CGX_OK on any rank
+// fails the call on all of them (its own message on that rank, the rank's
+// number on the others). A rank always enters this collective, whatever
+// happened to it before: none fails alone and leaves its peers waiting.
+struct PcVerdict {
+  unsigned long long count, first;
+  int rc, pad;
+};
+int pc_agree(cgx_csr *A, int mine_rc, unsigned long long (&h)[2], const char *what) {
+  cgx_ctx *ctx = A->ctx;
+  const std::string why = mine_rc ? cgx_last_error() : "";
+  PcVerdict v{mine_rc ? 0 : h[0],
+              (!mine_rc && h[0]) ? h[1] + (unsigned long long)A->row_begin : ~0ull, mine_rc, 0};
+  std::vector<PcVerdict> all((size_t)ctx->world);
+  int rc = comm_allgather(ctx, &v, sizeof(v), all.data());
+  if (rc) return rc;
+  h[0] = 0;
+  h[1] = ~0ull;
+  int bad_rank = -1;
+  for (int q = 0; q < ctx->world; ++q) {
+    h[0] += all[q].count;
+    h[1] = std::min(h[1], all[q].first);
+    if (all[q].rc && bad_rank < 0) bad_rank = q;
+  }
+  if (mine_rc) {
+    set_error("%s", why.c_str());
+    return mine_rc;
+  }
+  if (bad_rank >= 0) {
+    set_error("%s failed on rank %d (status %d there)", what, bad_rank, all[bad_rank].rc);
+    return all[bad_rank].rc;
+  }
+  return CGX_OK;
+}
+
+// the body of cgx_csr_diag_inv; pre_rc: what the caller's own checks came to
+// on this rank (partitioned: carried into the collective verdict)
+int diag_inv_impl(cgx_csr *A, void *d_out, int pre_rc) {
   DeviceGuard g(A->ctx->device);
   hipStream_t s = A->ctx->stream;
-  unsigned long long h[2];
-  int rc = pc_scan(A->ctx, h, [&](unsigned long long *bad) {
-    return A->dtype == CGX_F32 ? Launch<float>::diag_inv(A->dev, (float *)d_out, bad, s)
-                               : Launch<double>::diag_inv(A->dev, (double *)d_out, bad, s);
-  });
+  unsigned long long h[2] = {0, ~0ull};
+  int rc = pre_rc;
+  if (!rc && A->dev.n > 0)
+    rc = pc_scan(A->ctx, h, [&](unsigned long long *bad) {
+      return A->dtype == CGX_F32 ? Launch<float>::diag_inv(A->dev, (float *)d_out, bad, s)
+                                 : Launch<double>::diag_inv(A->dev, (double *)d_out, bad, s);
+    });
+  // (after cgx_csr_create_dist the columns are local: own rows first, so row
+  // i's diagonal entry is col == i, which is what k_diag_inv looks for)
+  if (A->dist) rc = pc_agree(A, rc, h, "cgx_csr_diag_inv");
   if (rc) return rc;
   CGX_REQUIRE(h[0] == 0, CGX_EINVAL,
               "cgx_csr_diag_inv: %llu row(s) without a positive, finite diagonal entry; the first "
               "is row %llu", h[0], h[1]);
   return CGX_OK;
+}
+}  // namespace
+
+extern "C" int cgx_csr_diag_inv(cgx_csr *A, void *d_out) {
+  CGX_REQUIRE(A, CGX_EINVAL, "NULL argument");
+  if (A->dist) {  // collective: a NULL d_out on one rank fails the call on all
+    int pre = CGX_OK;
+    if (!d_out) {
+      set_error("NULL argument");
+      pre = CGX_EINVAL;
+    }
+    return diag_inv_impl(A, d_out, pre);
+  }
+  CGX_REQUIRE(d_out, CGX_EINVAL, "NULL argument");
+  if (A->dev.n == 0) return CGX_OK;
+  return diag_inv_impl(A, d_out, CGX_OK);
 }
 
 extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
@@ -3297,12 +3396,57 @@ extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
   hipStream_t s = cg->ctx->stream;
   void *own = nullptr;
   const void *m = nullptr;
-  if (kind != CGX_PRECOND_NONE) {
+  if (kind != CGX_PRECOND_NONE && cg->A->dist) {
+    // partitioned: a collective call (every rank, the same kind). This rank's
+    // own checks do not return: their status travels in the one collective
+    // verdict of the scan, so the ranks fail or succeed together
+    cgx_csr *A = cg->A;
+    const size_t es = dtype_size(cg->dtype);
+    unsigned long long h[2] = {0, ~0ull};
+    int rc = CGX_OK, cur = 0;
+    (void)cgx_cg_get_mode(cg, &cur);
+    if (!(cg->mode_req == 0 || cg->mode_req == 1 || cg->mode_req == 3)) {
+      set_error("a preconditioner in mode %d: diagonal preconditioning runs in modes 1 and 3 "
+                "(auto resolves to 3)", cur);
+      rc = CGX_EUNSUPPORTED;
+    }
+    if (kind == CGX_PRECOND_JACOBI) {
+      if (!rc) {
+        hipError_t e = hipMalloc(&own, ((size_t)cg->n + 1) * es);
+        if (e != hipSuccess) rc = hip_fail(e, "cgx_cg_set_precond (Jacobi's m)");
+      }
+      rc = diag_inv_impl(A, own, rc);
+      m = own;
+    } else {
+      if (!rc && !d_minv) {
+        set_error("CGX_PRECOND_DIAGONAL needs d_minv");
+        rc = CGX_EINVAL;
+      }
+      if (!rc && ((uintptr_t)d_minv & 15) != 0) {
+        set_error("d_minv must be 16-byte aligned (the kernels read it in 16-byte lanes)");
+        rc = CGX_EINVAL;
+      }
+      if (!rc && cg->n > 0)
+        rc = pc_scan(cg->ctx, h, [&](unsigned long long *bad) {
+          return cg->dtype == CGX_F32
+                     ? Launch<float>::diag_check(cg->n, (const float *)d_minv, bad, s)
+                     : Launch<double>::diag_check(cg->n, (const double *)d_minv, bad, s);
+        });
+      rc = pc_agree(A, rc, h, "cgx_cg_set_precond");
+      if (!rc && h[0] != 0) {
+        set_error("cgx_cg_set_precond: %llu entr%s of d_minv not positive and finite; the first "
+                  "is entry %llu (global)", h[0], h[0] == 1 ? "y" : "ies", h[1]);
+        rc = CGX_EINVAL;
+      }
+      m = d_minv;
+    }
+    if (rc) {
+      if (own) (void)hipFree(own);
+      return rc;
+    }
+  } else if (kind != CGX_PRECOND_NONE) {
     int cur = 0;
     (void)cgx_cg_get_mode(cg, &cur);
-    CGX_REQUIRE(!cg->A->dist, CGX_EUNSUPPORTED,
-                "a preconditioner on a partitioned matrix: diagonal preconditioning runs on a "
-                "single device, in modes 1 and 3");
     CGX_REQUIRE(cg->mode_req == 0 || cg->mode_req == 1 || cg->mode_req == 3, CGX_EUNSUPPORTED,
                 "a preconditioner in mode %d: diagonal preconditioning runs in modes 1 and 3 "
                 "(auto resolves to 3)", cur);
@@ -3457,21 +3601,23 @@ extern "C" int cgx_cg_begin(cgx_cg *cg, const void *b, void *x, double tol,
     if (rc) return rc;
     xe = cg->Ap;
   }
-  CGX_REQUIRE(!cg->precond || (!A->dist && !cg->fused && !cg->fdefer && !cg->coop &&
-                               !cg->recompute && cg->minv),
+  CGX_REQUIRE(!cg->precond || (!cg->fused && !cg->fdefer && !cg->coop && !cg->recompute &&
+                               cg->minv),
               CGX_ESTATE, "a preconditioner is set but the solver is not in mode 1 or 3");
   rc = timed(cg, 0, s, [&] {
     // with a preconditioner a second launch overwrites p = m o r and reduces
-    // rz[0] = r.(m o r) (timed with the init kernel, index 0)
+    // rz[0] = r.(m o r) (timed with the init kernel, index 0); on a
+    // partitioned matrix over the own rows, all-reduced below, so the first
+    // body's halo push carries p = m o r
     if (cg->dtype == CGX_F32) {
       hipError_t e = Launch<float>::cg_init(A->dev, (const float *)xe, (const float *)b,
                                             (float *)cg->r, (float *)cg->p,
                                             (CgScalars<float> *)cg->st, (RedWs<float> *)cg->ws,
                                             (float)tol, cap, s);
       if (e == hipSuccess && cg->precond)
-        e = Launch<float>::pc_init(cg->n, (const float *)cg->r, (const float *)cg->minv,
-                                   (float *)cg->p, (CgScalars<float> *)cg->st,
-                                   (RedWs<float> *)cg->ws, s);
+        e = (A->dist ? Launch<float>::pc_init_dist : Launch<float>::pc_init)(
+            cg->n, (const float *)cg->r, (const float *)cg->minv, (float *)cg->p,
+            (CgScalars<float> *)cg->st, (RedWs<float> *)cg->ws, s);
       return e;
     }
     hipError_t e = Launch<double>::cg_init(A->dev, (const double *)xe, (const double *)b,
@@ -3479,9 +3625,9 @@ extern "C" int cgx_cg_begin(cgx_cg *cg, const void *b, void *x, double tol,
                                            (CgScalars<double> *)cg->st, (RedWs<double> *)cg->ws,
                                            tol, cap, s);
     if (e == hipSuccess && cg->precond)
-      e = Launch<double>::pc_init(cg->n, (const double *)cg->r, (const double *)cg->minv,
-                                  (double *)cg->p, (CgScalars<double> *)cg->st,
-                                  (RedWs<double> *)cg->ws, s);
+      e = (A->dist ? Launch<double>::pc_init_dist : Launch<double>::pc_init)(
+          cg->n, (const double *)cg->r, (const double *)cg->minv, (double *)cg->p,
+          (CgScalars<double> *)cg->st, (RedWs<double> *)cg->ws, s);
     return e;
   });
   if (rc) return rc;
@@ -3492,16 +3638,28 @@ extern "C" int cgx_cg_begin(cgx_cg *cg, const void *b, void *x, double tol,
       auto *st = (CgScalars<float> *)cg->st;
       rc = peer_allreduce<float>(A, ((RedWs<float> *)cg->ws)->rr_part, 1, &st->rxr[0], nullptr,
                                  0, s, 0);
+      if (!rc && cg->precond)  // and r.z's pair (k_pc_init_dist) into rz[0]
+        rc = peer_allreduce<float>(A, ((RedWs<float> *)cg->ws)->rz_part, 1, &st->rz[0], nullptr,
+                                   0, s, 0);
     } else {
       auto *st = (CgScalars<double> *)cg->st;
       rc = peer_allreduce<double>(A, ((RedWs<double> *)cg->ws)->rr_part, 1, &st->rxr[0],
                                   nullptr, 0, s, 0);
+      if (!rc && cg->precond)
+        rc = peer_allreduce<double>(A, ((RedWs<double> *)cg->ws)->rz_part, 1, &st->rz[0],
+                                    nullptr, 0, s, 0);
     }
     if (rc) return rc;
   } else if (A->dist) {
     const size_t off = cg->dtype == CGX_F32 ? offsetof(CgScalars<float>, rxr)
                                             : offsetof(CgScalars<double>, rxr);
     if ((rc = dist_allreduce_scalar(cg->ctx, (char *)cg->st + off, cg->dtype, 1, s))) return rc;
+    if (cg->precond) {
+      const size_t offz = cg->dtype == CGX_F32 ? offsetof(CgScalars<float>, rz)
+                                               : offsetof(CgScalars<double>, rz);
+      if ((rc = dist_allreduce_scalar(cg->ctx, (char *)cg->st + offz, cg->dtype, 1, s)))
+        return rc;
+    }
   }
   cg->slot = 0;
   cg->begun = true;

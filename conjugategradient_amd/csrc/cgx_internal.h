@@ -54,6 +54,12 @@ template <typename T> struct CgScalars {
   // true r.r for the stop rule). Last, so the offsets above do not move; the
   // host's polls copy the struct up to here (cgx_abi.cpp poll_state).
   T rz[4];
+  // a preconditioned body on a partitioned matrix whose all-reduces are steps
+  // of their own (host, RCCL, the peer one-waiter form): the world {r.r, r.z}
+  // of the body in slot s at rrz[2 s], rrz[2 s + 1], adjacent so that one
+  // collective of two values carries both; the p update reads them here.
+  // Appended as rz was: no offset above moves.
+  T rrz[8];
 };
 
 // Grid-reduction workspace. Arrivals are sharded over kRedGroups tickets
@@ -408,6 +414,25 @@ template <typename T> struct Launch {
   static hipError_t update_p_defer_pc(int64_t n, T *x, const T *p, T *pn, T *const P[4],
                                       const T *r, const T *m, CgScalars<T> *st, int slot,
                                       RedWs<T> *ws, int np_rr, hipStream_t s, int rev, bool m_nt);
+  // the same kernels on a partitioned matrix (the rank's own rows). peer: the
+  // device peer transport's fused form, the world p.Ap and {r.r, r.z} summed
+  // inside the kernels (np_*: the local partials); nullptr: the world values
+  // read from the scalar ring (pAp[slot], rrz[2 slot..]), where a separate
+  // all-reduce step put them. m through plain loads.
+  static hipError_t pc_init_dist(int64_t n, const T *r, const T *m, T *p, CgScalars<T> *st,
+                                 RedWs<T> *ws, hipStream_t s);
+  static hipError_t update_r_pc_dist(int64_t n, T *r, const T *Ap, const T *m, CgScalars<T> *st,
+                                     int slot, RedWs<T> *ws, hipStream_t s, int np_pap, int rev,
+                                     const PeerDev *peer);
+  static hipError_t update_xp_pc_dist(int64_t n, T *x, T *p, const T *r, const T *m,
+                                      CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr,
+                                      hipStream_t s, int rev, const PeerDev *peer);
+  static hipError_t update_p_defer_pc_dist(int64_t n, T *x, const T *p, T *pn, T *const P[4],
+                                           const T *r, const T *m, CgScalars<T> *st, int slot,
+                                           RedWs<T> *ws, int np_rr, hipStream_t s, int rev,
+                                           const PeerDev *peer);
+  // dst[0], dst[1] = the sums of part_a, part_b (one launch; k_finalize twice)
+  static hipError_t finalize2(const T *part_a, const T *part_b, int np, T *dst, hipStream_t s);
   // out[i] = 1 / (sum of row i's entries with col == i); bad[0] counts the
   // rows whose diagonal is missing, not positive or not finite, bad[1] is the
   // lowest such row (the caller presets {0, ~0})

@@ -4998,12 +4998,43 @@ __global__ __launch_bounds__(kBlock) void k_pc_init(int64_t n, const T *__restri
   if (grid_reduce_dd(acc, ws, red, &flag) && threadIdx.x == 0) st->rz[0] = acc.value();
 }
 
+// k_pc_init on a partitioned matrix (the rank's own rows): rz[0] is the
+// local value until the init all-reduce replaces it; its double-length pair
+// goes to rz_part[0..1] as well, where the peer transport's all-reduce takes
+// it (as k_cg_init leaves r.r's pair in rr_part[0..1])
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_pc_init_dist(int64_t n, const T *__restrict__ r,
+                                                         const T *__restrict__ m,
+                                                         T *__restrict__ p, CgScalars<T> *st,
+                                                         RedWs<T> *ws) {
+  __shared__ T red[8];
+  __shared__ int flag;
+  Dd<T> acc(T(0));
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    const T rv = r[i];
+    const T z = m[i] * rv;
+    p[i] = z;
+    acc += rv * z;
+  }
+  if (grid_reduce_dd(acc, ws, red, &flag) && threadIdx.x == 0) {
+    st->rz[0] = acc.value();
+    ws->rz_part[0] = acc.hi;
+    ws->rz_part[1] = acc.lo;
+  }
+}
+
 // r = r - alpha Ap with alpha = rz / p.Ap; r.r and r.(m o r) in one sweep
 // (update_r_body's single-device, non-fused form)
-template <typename T, bool SNT, bool MNT, int KP>
+// D (partitioned matrices): 0 one device; 1 the device peer transport's fused
+// form, p.Ap all-reduced here (peerdev::world_sum, tag base + 1, as
+// update_r_body's PEER); 2 the world p.Ap read from st->pAp[slot], where a
+// separate all-reduce step put it (host, RCCL, the peer one-waiter form)
+template <typename T, bool SNT, bool MNT, int KP, int D = 0>
 __device__ __forceinline__ void update_r_pc_body(int64_t n, T *r, const T *__restrict__ Ap,
                                                  const T *__restrict__ m, CgScalars<T> *st,
-                                                 int slot, RedWs<T> *ws, int np_pap, int rev) {
+                                                 int slot, RedWs<T> *ws, int np_pap, int rev,
+                                                 const PeerDev *P = nullptr) {
   const auto *cst = (const __attribute__((address_space(4))) CgScalars<T> *)st;
   const bool act = cst->active[slot] != 0;  // branched on after the first loads
   __shared__ T red[8];
@@ -5020,8 +5051,10 @@ __device__ __forceinline__ void update_r_pc_body(int64_t n, T *r, const T *__res
   auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
   int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const T rz = cst->rz[slot];
+  T pAp_st = T(0);
+  if constexpr (D == 2) pAp_st = cst->pAp[slot];
   Dd<T> pl[KP];
-  parts_load(ws->pap_part, np_pap, pl);
+  if constexpr (D != 2) parts_load(ws->pap_part, np_pap, pl);
   V rv[kUR], av[kUR], mv[kUR];
 #pragma unroll
   for (int u = 0; u < kUR; ++u) {  // clamped: no branch
@@ -5032,13 +5065,34 @@ __device__ __forceinline__ void update_r_pc_body(int64_t n, T *r, const T *__res
   }
   if (!act) {
     keep(rz);
-    keep(pl);
+    if constexpr (D == 2) keep(pAp_st);
+    if constexpr (D != 2) keep(pl);
     keep(rv);
     keep(av);
     keep(mv);
     return;
   }
-  const T pAp = parts_sum_dd(pl, np_pap, red).value();
+  T pAp;
+  if constexpr (D == 2) {
+    pAp = pAp_st;
+  } else {
+    const Dd<T> pd = parts_sum_dd(pl, np_pap, red);
+    pAp = pd.value();
+    if constexpr (D == 1) {
+      __shared__ double wres;
+      __shared__ int wok;
+      if (P->state->fault) {  // an earlier spin timed out: stop this body too
+        peer_fault(st, slot, P);
+        return;
+      }
+      if (!peerdev::world_sum(Dd<double>((double)pd.hi, (double)pd.lo),
+                              P->state->arb[slot & 1] + 1, *P, &wres, &wok)) {
+        peer_fault(st, slot, P);
+        return;
+      }
+      pAp = (T)wres;
+    }
+  }
   const T alpha = rz / pAp;
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // the record; the deferred x update
     st->pAp[slot] = pAp;
@@ -5103,6 +5157,32 @@ __global__ __launch_bounds__(kBlock) void k_update_r_pc(int64_t n, T *r, const T
     update_r_pc_body<T, true, MNT, KP>(n, r, Ap, m, st, slot, ws, np_pap, rev);
   else
     update_r_pc_body<T, false, MNT, KP>(n, r, Ap, m, st, slot, ws, np_pap, rev);
+}
+
+// the partitioned forms (update_r_pc_body's D): the peer transport's fused
+// form, and the form behind a separate all-reduce step (np_pap unused)
+template <typename T, int KP>
+__global__ __launch_bounds__(kBlock) void k_update_r_pc_peer(int64_t n, T *r,
+                                                             const T *__restrict__ Ap,
+                                                             const T *__restrict__ m,
+                                                             CgScalars<T> *st, int slot,
+                                                             RedWs<T> *ws, int np_pap, int rev,
+                                                             PeerDev P) {
+  if (stream_nt<T>(n))
+    update_r_pc_body<T, true, false, KP, 1>(n, r, Ap, m, st, slot, ws, np_pap, rev, &P);
+  else
+    update_r_pc_body<T, false, false, KP, 1>(n, r, Ap, m, st, slot, ws, np_pap, rev, &P);
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_update_r_pc_ring(int64_t n, T *r,
+                                                             const T *__restrict__ Ap,
+                                                             const T *__restrict__ m,
+                                                             CgScalars<T> *st, int slot,
+                                                             RedWs<T> *ws, int rev) {
+  if (stream_nt<T>(n))
+    update_r_pc_body<T, true, false, 4, 2>(n, r, Ap, m, st, slot, ws, 0, rev);
+  else
+    update_r_pc_body<T, false, false, 4, 2>(n, r, Ap, m, st, slot, ws, 0, rev);
 }
 
 // the stop rule and the records of a preconditioned body (workgroup 0,
@@ -5191,25 +5271,163 @@ __global__ __launch_bounds__(kBlock) void k_update_xp_pc(int64_t n, T *__restric
   }
 }
 
+// A partitioned preconditioned body's world {r.r, r.z} in the peer
+// transport's fused form: this rank's two double-length sums all-reduced
+// together under tag base + 2 (peerdev::world_sum2; the plain body's r.r
+// all-reduce, update_xp_body's PEER). false: the body stops (fault raised).
+template <typename T>
+__device__ __forceinline__ bool pc_world_pair(Dd<T> rd, Dd<T> zd, CgScalars<T> *st, int slot,
+                                              const PeerDev *P, T *rr, T *rzn) {
+  __shared__ double wres2[2];
+  __shared__ int wok2;
+  if (P->state->fault) {  // an earlier spin timed out: stop this body too
+    peer_fault(st, slot, P);
+    return false;
+  }
+  if (!peerdev::world_sum2(Dd<double>((double)rd.hi, (double)rd.lo),
+                           Dd<double>((double)zd.hi, (double)zd.lo),
+                           P->state->arb[slot & 1] + 2, *P, wres2, &wok2)) {
+    peer_fault(st, slot, P);
+    return false;
+  }
+  *rr = (T)wres2[0];
+  *rzn = (T)wres2[1];
+  return true;
+}
+// the next body's tag base (workgroup 0, thread 0, after the stop rule)
+__device__ __forceinline__ void pc_next_base(int slot, const PeerDev *P) {
+  const unsigned long long t = P->state->arb[slot & 1] + 2;
+  P->state->ar = t;
+  P->state->arb[(slot + 1) & 1] = t;
+}
+
+// mode 1 on a partitioned matrix: k_update_xp_pc statement for statement,
+// with the world {r.r, r.z} all-reduced here (D == 1) or read from the
+// scalar ring (D == 2: st->rrz, put there by the separate all-reduce step)
+template <typename T, int D>
+__device__ __forceinline__ void update_xp_pc_dist_body(int64_t n, T *__restrict__ x,
+                                                       T *__restrict__ p,
+                                                       const T *__restrict__ r,
+                                                       const T *__restrict__ m,
+                                                       CgScalars<T> *st, int slot, RedWs<T> *ws,
+                                                       int np_rr, int rev, const PeerDev *P) {
+  const int nxt = (slot + 1) & 3;
+  if (!st->active[slot]) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->active[nxt] = 0;
+    return;
+  }
+  __shared__ T red[8];
+  __shared__ T redz[8];
+  const T rxr = st->rxr[slot];
+  const T rz = st->rz[slot];
+  const T alpha = rz / st->pAp[slot];
+  T rr, rzn;
+  if constexpr (D == 2) {
+    rr = st->rrz[2 * slot];
+    rzn = st->rrz[2 * slot + 1];
+  } else {
+    const Dd<T> rd = sum_parts_dd(ws->rr_part, np_rr, red);
+    const Dd<T> zd = sum_parts_dd(ws->rz_part, np_rr, redz);
+    if (!pc_world_pair(rd, zd, st, slot, P, &rr, &rzn)) return;
+  }
+  const T beta = rzn / rz;
+  using V = typename Vec2<T>::V;
+  const int64_t n2 = n >> 1;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  V *x2 = reinterpret_cast<V *>(x);
+  V *p2 = reinterpret_cast<V *>(p);
+  const V *rv2 = reinterpret_cast<const V *>(r);
+  const V *m2 = reinterpret_cast<const V *>(m);
+  auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  for (; i + 3 * stride < n2; i += 4 * stride) {
+    V xv[4], pv[4], rv[4], mv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      xv[u] = x2[E(i + u * stride)];
+      pv[u] = p2[E(i + u * stride)];
+      rv[u] = rv2[E(i + u * stride)];
+      mv[u] = m2[E(i + u * stride)];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      xv[u].x = xv[u].x + alpha * pv[u].x;
+      xv[u].y = xv[u].y + alpha * pv[u].y;
+      pv[u].x = mv[u].x * rv[u].x + beta * pv[u].x;
+      pv[u].y = mv[u].y * rv[u].y + beta * pv[u].y;
+      x2[E(i + u * stride)] = xv[u];
+      p2[E(i + u * stride)] = pv[u];
+    }
+  }
+  for (; i < n2; i += stride) {
+    V xv = x2[E(i)], pv = p2[E(i)];
+    const V rv = rv2[E(i)];
+    const V mv = m2[E(i)];
+    xv.x = xv.x + alpha * pv.x;
+    xv.y = xv.y + alpha * pv.y;
+    pv.x = mv.x * rv.x + beta * pv.x;
+    pv.y = mv.y * rv.y + beta * pv.y;
+    x2[E(i)] = xv;
+    p2[E(i)] = pv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (n & 1) {
+      const T pv = p[n - 1];
+      x[n - 1] = x[n - 1] + alpha * pv;
+      p[n - 1] = m[n - 1] * r[n - 1] + beta * pv;
+    }
+    pc_stop_rule(st, slot, rxr, rr, rzn);
+    if constexpr (D == 1) pc_next_base(slot, P);
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_update_xp_pc_peer(int64_t n, T *__restrict__ x,
+                                                              T *__restrict__ p,
+                                                              const T *__restrict__ r,
+                                                              const T *__restrict__ m,
+                                                              CgScalars<T> *st, int slot,
+                                                              RedWs<T> *ws, int np_rr, int rev,
+                                                              PeerDev P) {
+  update_xp_pc_dist_body<T, 1>(n, x, p, r, m, st, slot, ws, np_rr, rev, &P);
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_update_xp_pc_ring(int64_t n, T *__restrict__ x,
+                                                              T *__restrict__ p,
+                                                              const T *__restrict__ r,
+                                                              const T *__restrict__ m,
+                                                              CgScalars<T> *st, int slot,
+                                                              RedWs<T> *ws, int rev) {
+  update_xp_pc_dist_body<T, 2>(n, x, p, r, m, st, slot, ws, 0, rev, nullptr);
+}
+
 // mode 3: p_{k+1} = m o r + beta p_k into the next p buffer, the stop rule,
 // and in slot 3 (FLUSH) the group's x updates (update_p_defer_body's
 // single-device form; the alphas it applies are update_r_pc's rz / p.Ap)
-template <typename T, bool FLUSH, bool SNT, bool MNT>
+// D: the partitioned forms, as update_xp_pc_dist_body's
+template <typename T, bool FLUSH, bool SNT, bool MNT, int D = 0>
 __device__ __forceinline__ void update_p_defer_pc_body(int64_t n, T *__restrict__ x, const T *p,
                                                        T *pn, const T *P0, const T *P1,
                                                        const T *P2, const T *__restrict__ r,
                                                        const T *__restrict__ m,
                                                        CgScalars<T> *st, int slot, RedWs<T> *ws,
-                                                       int np_rr, int rev) {
+                                                       int np_rr, int rev,
+                                                       const PeerDev *PD = nullptr) {
   const int nxt = (slot + 1) & 3;
   // the flag, rxr, rz and both dots' partials in one round trip
   const auto *cst = (const __attribute__((address_space(4))) CgScalars<T> *)st;
   const bool act = cst->active[slot] != 0;
   const T rxr = cst->rxr[slot];
   const T rz = cst->rz[slot];
+  T rr_st = T(0), rz_st = T(0);
+  if constexpr (D == 2) {
+    rr_st = cst->rrz[2 * slot];
+    rz_st = cst->rrz[2 * slot + 1];
+  }
   Dd<T> pl[kPartsPerThread], plz[kPartsPerThread];
-  parts_load_np(ws->rr_part, np_rr, pl);
-  parts_load_np(ws->rz_part, np_rr, plz);
+  if constexpr (D != 2) {
+    parts_load_np(ws->rr_part, np_rr, pl);
+    parts_load_np(ws->rz_part, np_rr, plz);
+  }
   using V = typename Vec2<T>::V;
   const int64_t n2 = n >> 1;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
@@ -5235,8 +5453,13 @@ __device__ __forceinline__ void update_p_defer_pc_body(int64_t n, T *__restrict_
   if (!act) {
     keep(rxr);
     keep(rz);
-    keep(pl);
-    keep(plz);
+    if constexpr (D == 2) {
+      keep(rr_st);
+      keep(rz_st);
+    } else {
+      keep(pl);
+      keep(plz);
+    }
     if constexpr (!FLUSH) {
       keep(pv0);
       keep(rv0);
@@ -5247,8 +5470,19 @@ __device__ __forceinline__ void update_p_defer_pc_body(int64_t n, T *__restrict_
   }
   __shared__ T red[8];
   __shared__ T redz[8];
-  const T rr = parts_sum_dd(pl, np_rr, red).value();
-  const T rzn = parts_sum_dd(plz, np_rr, redz).value();
+  T rr, rzn;
+  if constexpr (D == 2) {
+    rr = rr_st;
+    rzn = rz_st;
+  } else {
+    const Dd<T> rd = parts_sum_dd(pl, np_rr, red);
+    const Dd<T> zd = parts_sum_dd(plz, np_rr, redz);
+    rr = rd.value();
+    rzn = zd.value();
+    if constexpr (D == 1) {
+      if (!pc_world_pair(rd, zd, st, slot, PD, &rr, &rzn)) return;
+    }
+  }
   const T beta = rzn / rz;
   // slot-3 flush: alphas and skips of the group, written by earlier launches
   T a[4] = {T(0), T(0), T(0), T(0)};
@@ -5330,7 +5564,32 @@ __device__ __forceinline__ void update_p_defer_pc_body(int64_t n, T *__restrict_
     } else {
       st->ran[slot] = 1;
     }
+    if constexpr (D == 1) pc_next_base(slot, PD);
   }
+}
+template <typename T, bool FLUSH>
+__global__ __launch_bounds__(kBlock) void k_update_p_defer_pc_peer(
+    int64_t n, T *__restrict__ x, const T *p, T *pn, const T *P0, const T *P1, const T *P2,
+    const T *__restrict__ r, const T *__restrict__ m, CgScalars<T> *st, int slot, RedWs<T> *ws,
+    int np_rr, int rev, PeerDev PD) {
+  if (stream_nt<T>(n))
+    update_p_defer_pc_body<T, FLUSH, true, false, 1>(n, x, p, pn, P0, P1, P2, r, m, st, slot, ws,
+                                                     np_rr, rev, &PD);
+  else
+    update_p_defer_pc_body<T, FLUSH, false, false, 1>(n, x, p, pn, P0, P1, P2, r, m, st, slot,
+                                                      ws, np_rr, rev, &PD);
+}
+template <typename T, bool FLUSH>
+__global__ __launch_bounds__(kBlock) void k_update_p_defer_pc_ring(
+    int64_t n, T *__restrict__ x, const T *p, T *pn, const T *P0, const T *P1, const T *P2,
+    const T *__restrict__ r, const T *__restrict__ m, CgScalars<T> *st, int slot, RedWs<T> *ws,
+    int rev) {
+  if (stream_nt<T>(n))
+    update_p_defer_pc_body<T, FLUSH, true, false, 2>(n, x, p, pn, P0, P1, P2, r, m, st, slot, ws,
+                                                     0, rev);
+  else
+    update_p_defer_pc_body<T, FLUSH, false, false, 2>(n, x, p, pn, P0, P1, P2, r, m, st, slot,
+                                                      ws, 0, rev);
 }
 template <typename T, bool FLUSH, bool MNT>
 __global__ __launch_bounds__(kBlock) void k_update_p_defer_pc(
@@ -5396,6 +5655,22 @@ __global__ __launch_bounds__(kBlock) void k_finalize(const T *__restrict__ part,
   __shared__ T red[8];
   const T v = sum_parts(part, np, red);
   if (threadIdx.x == 0) *dst = v;
+}
+// k_finalize for a preconditioned body's two dots in one launch: dst[0],
+// dst[1] = the sums of part_a, part_b (np pairs each), adjacent for the one
+// all-reduce of two values behind it
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_finalize2(const T *__restrict__ part_a,
+                                                      const T *__restrict__ part_b, int np,
+                                                      T *dst) {
+  __shared__ T red[8];
+  __shared__ T redb[8];
+  const T va = sum_parts(part_a, np, red);
+  const T vb = sum_parts(part_b, np, redb);
+  if (threadIdx.x == 0) {
+    dst[0] = va;
+    dst[1] = vb;
+  }
 }
 
 template <typename T> __global__ void k_mark_defer(CgScalars<T> *st) {
@@ -6242,6 +6517,60 @@ hipError_t Launch<T>::update_p_defer_pc(int64_t n, T *x, const T *p, T *pn, T *c
   if (m_nt) CGX_UPPC(false, true);
   CGX_UPPC(false, false);
 #undef CGX_UPPC
+}
+// the partitioned forms: peer != nullptr the peer transport's fused form
+// (np the local partials), else the world values from the scalar ring
+template <typename T>
+hipError_t Launch<T>::pc_init_dist(int64_t n, const T *r, const T *m, T *p, CgScalars<T> *st,
+                                   RedWs<T> *ws, hipStream_t s) {
+  CGX_LAUNCH(k_pc_init_dist<T>, grid_elems(n, kGridUpdateP), n, r, m, p, st, ws);
+}
+template <typename T>
+hipError_t Launch<T>::update_r_pc_dist(int64_t n, T *r, const T *Ap, const T *m,
+                                       CgScalars<T> *st, int slot, RedWs<T> *ws, hipStream_t s,
+                                       int np_pap, int rev, const PeerDev *peer) {
+  const int g = grid_elems(n, kGridUpdateR);
+  if (!peer) CGX_LAUNCH(k_update_r_pc_ring<T>, g, n, r, Ap, m, st, slot, ws, rev);
+  if (np_pap < 1) return hipErrorInvalidValue;
+  if (np_pap <= 4 * kBlock)
+    CGX_LAUNCH((k_update_r_pc_peer<T, 4>), g, n, r, Ap, m, st, slot, ws, np_pap, rev, *peer);
+  if (np_pap <= 8 * kBlock)
+    CGX_LAUNCH((k_update_r_pc_peer<T, 8>), g, n, r, Ap, m, st, slot, ws, np_pap, rev, *peer);
+  CGX_LAUNCH((k_update_r_pc_peer<T, kPartsPerThread>), g, n, r, Ap, m, st, slot, ws, np_pap, rev,
+             *peer);
+}
+template <typename T>
+hipError_t Launch<T>::update_xp_pc_dist(int64_t n, T *x, T *p, const T *r, const T *m,
+                                        CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr,
+                                        hipStream_t s, int rev, const PeerDev *peer) {
+  const int g = grid_elems(n, kGridUpdateP);
+  if (!peer) CGX_LAUNCH(k_update_xp_pc_ring<T>, g, n, x, p, r, m, st, slot, ws, rev);
+  if (np_rr < 1) return hipErrorInvalidValue;
+  CGX_LAUNCH(k_update_xp_pc_peer<T>, g, n, x, p, r, m, st, slot, ws, np_rr, rev, *peer);
+}
+template <typename T>
+hipError_t Launch<T>::update_p_defer_pc_dist(int64_t n, T *x, const T *p, T *pn, T *const P[4],
+                                             const T *r, const T *m, CgScalars<T> *st, int slot,
+                                             RedWs<T> *ws, int np_rr, hipStream_t s, int rev,
+                                             const PeerDev *peer) {
+  const int g = grid_elems(n, kGridUpdateP);
+  if (!peer && slot == 3)
+    CGX_LAUNCH((k_update_p_defer_pc_ring<T, true>), g, n, x, p, pn, (const T *)P[0],
+               (const T *)P[1], (const T *)P[2], r, m, st, slot, ws, rev);
+  if (!peer)
+    CGX_LAUNCH((k_update_p_defer_pc_ring<T, false>), g, n, x, p, pn, (const T *)P[0],
+               (const T *)P[1], (const T *)P[2], r, m, st, slot, ws, rev);
+  if (np_rr < 1) return hipErrorInvalidValue;
+  if (slot == 3)
+    CGX_LAUNCH((k_update_p_defer_pc_peer<T, true>), g, n, x, p, pn, (const T *)P[0],
+               (const T *)P[1], (const T *)P[2], r, m, st, slot, ws, np_rr, rev, *peer);
+  CGX_LAUNCH((k_update_p_defer_pc_peer<T, false>), g, n, x, p, pn, (const T *)P[0],
+             (const T *)P[1], (const T *)P[2], r, m, st, slot, ws, np_rr, rev, *peer);
+}
+template <typename T>
+hipError_t Launch<T>::finalize2(const T *part_a, const T *part_b, int np, T *dst, hipStream_t s) {
+  CGX_GGL(k_finalize2<T>, dim3(1), dim3(kBlock), 0, s, part_a, part_b, np, dst);
+  return hipGetLastError();
 }
 template <typename T>
 hipError_t Launch<T>::diag_inv(const CsrDev &A, T *out, unsigned long long *bad, hipStream_t s) {

@@ -96,10 +96,14 @@ struct PeerDev {  // kernel argument (by value)
 };
 // mailbox layout inside a rank's ctl allocation: val[2][kPeerMax] double-
 // length pairs (hi, lo), tag[2][kPeerMax] u64 (parity = tag & 1), then
-// flag[kPeerMax][kPushWG] u64
+// flag[kPeerMax][kPushWG] u64, then val2[2][kPeerMax] pairs: the second pair
+// of a paired all-reduce (a preconditioned body's {r.r, r.z}; the first pair
+// sits in val, both under the one tag). Appended, so the offsets before it
+// are those of the plain transport
 constexpr int kPeerTagOff = 4 * kPeerMax * 8;
 constexpr int kPeerFlagOff = 6 * kPeerMax * 8;
-constexpr size_t kPeerCtlBytes = kPeerFlagOff + (size_t)kPeerMax * kPushWG * 8;
+constexpr int kPeerVal2Off = kPeerFlagOff + kPeerMax * kPushWG * 8;
+constexpr size_t kPeerCtlBytes = kPeerVal2Off + (size_t)4 * kPeerMax * 8;
 struct Peer {
   bool on = false;
   void *ctl = nullptr;    // this rank's ctl (uncached, IPC-exported)
@@ -315,5 +319,10 @@ template <typename T> int peer_wait_one(cgx_csr *A, CgScalars<T> *st, int slot, 
 // which: 0 setup / init, 1 and 2 the body's p.Ap and r.r (k_peer_allreduce)
 template <typename T> int peer_allreduce(cgx_csr *A, const T *part, int np, T *dst,
                                          CgScalars<T> *st, int slot, hipStream_t s, int which);
+// two dots under one tag (dst[0], dst[1]; k_peer_allreduce2): which 2, a
+// preconditioned body's {r.r, r.z}; 0 the self-test's
+template <typename T> int peer_allreduce2(cgx_csr *A, const T *part_a, const T *part_b, int np,
+                                          T *dst, CgScalars<T> *st, int slot, hipStream_t s,
+                                          int which);
 int peer_destroy(cgx_csr *A);
 }  // namespace cgx

@@ -18,7 +18,9 @@
 //                     and a tag into every rank's mailbox, polls its own
 //                     mailbox until every rank's tag arrived, and sums the
 //                     world values IN RANK ORDER — bit-identical on all ranks,
-//                     so alpha, beta and the stop rule agree everywhere.
+//                     so alpha, beta and the stop rule agree everywhere;
+//   k_peer_allreduce2 the same for two dots under one tag: the {r.r, r.z}
+//                     pair of a preconditioned body.
 //
 // Landing buffers, mailboxes and flags are uncached device memory
 // (hipDeviceMallocUncached): remote stores and local loads meet in HBM with
@@ -35,8 +37,9 @@
 // cgx_dist_peer_enable builds the transport collectively over the setup
 // transport (RCCL or the host one) and checks it against that transport:
 // a halo exchange of a known vector must match bit for bit, and three
-// all-reduces of known values must be exact. All ranks agree on the outcome;
-// on any failure the partitioned solver keeps the setup transport.
+// all-reduces of known values and one paired all-reduce must be exact. All
+// ranks agree on the outcome; on any failure the partitioned solver keeps the
+// setup transport.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -151,6 +154,83 @@ __global__ __launch_bounds__(kBlock) void k_peer_allreduce(const T *__restrict__
   if (which == 2) P.state->arb[(slot + 1) & 1] = tag;
 }
 
+// k_peer_allreduce2: k_peer_allreduce for two dots under one tag (the
+// one-waiter form of a preconditioned body: r.r and r.z, which == 2; which
+// == 0 in the self-test). dst[0], dst[1] = the world sums of part_a, part_b
+// (np pairs each); the second pair travels in the mailbox's val2 area. One
+// launch, one tag: the body's launches and round trips are the plain body's.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_peer_allreduce2(const T *__restrict__ part_a,
+                                                             const T *__restrict__ part_b, int np,
+                                                             T *dst, CgScalars<T> *st, int slot,
+                                                             PeerDev P, int which) {
+  __shared__ double red[2 * (kBlock / 64)];
+  __shared__ double redb[2 * (kBlock / 64)];
+  __shared__ int ok_s;
+  if (skip_body(st, slot, P.state)) return;
+  Dd<double> v(0.0), vb(0.0);
+  for (int k = threadIdx.x; k < np; k += kBlock) {
+    v += Dd<double>((double)part_a[2 * k], (double)part_a[2 * k + 1]);
+    vb += Dd<double>((double)part_b[2 * k], (double)part_b[2 * k + 1]);
+  }
+  v = wave_sum_dd(v);
+  vb = wave_sum_dd(vb);
+  if ((threadIdx.x & 63) == 0) {
+    red[2 * (threadIdx.x >> 6)] = v.hi;
+    red[2 * (threadIdx.x >> 6) + 1] = v.lo;
+    redb[2 * (threadIdx.x >> 6)] = vb.hi;
+    redb[2 * (threadIdx.x >> 6) + 1] = vb.lo;
+  }
+  __syncthreads();
+  Dd<double> mine(red[0], red[1]), mineb(redb[0], redb[1]);
+  for (int w = 1; w < kBlock / 64; ++w) {
+    mine += Dd<double>(red[2 * w], red[2 * w + 1]);
+    mineb += Dd<double>(redb[2 * w], redb[2 * w + 1]);
+  }
+  const unsigned long long tag = which ? P.state->arb[slot & 1] + which : P.state->ar + 1;
+  const int par = (int)(tag & 1);
+  if (threadIdx.x < 64) {
+    bool ok = true;
+    if ((int)threadIdx.x < P.world) {
+      char *box = P.ctl[threadIdx.x];
+      double *val = reinterpret_cast<double *>(box) + 2 * (par * kPeerMax + P.rank);
+      double *val2 = reinterpret_cast<double *>(box + kPeerVal2Off) + 2 * (par * kPeerMax + P.rank);
+      st_sysd(val, mine.hi);
+      st_sysd(val + 1, mine.lo);
+      st_sysd(val2, mineb.hi);
+      st_sysd(val2 + 1, mineb.lo);
+      __threadfence_system();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      st_sys(reinterpret_cast<unsigned long long *>(box + kPeerTagOff) + par * kPeerMax + P.rank,
+             tag);
+      const auto *tags = reinterpret_cast<const unsigned long long *>(P.ctl[P.rank] + kPeerTagOff);
+      ok = spin_ge(tags + par * kPeerMax + threadIdx.x, tag, P.spin_ticks);
+    }
+    ok = __all(ok);
+    if (threadIdx.x == 0) ok_s = ok;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (!ok_s) {
+    raise_fault(st, slot, P.state);
+    return;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+  const double *vals = reinterpret_cast<const double *>(P.ctl[P.rank]) + 2 * par * kPeerMax;
+  const double *vals2 =
+      reinterpret_cast<const double *>(P.ctl[P.rank] + kPeerVal2Off) + 2 * par * kPeerMax;
+  Dd<double> s(0.0), sb(0.0);
+  for (int q = 0; q < P.world; ++q) {
+    s += Dd<double>(ld_sysd(vals + 2 * q), ld_sysd(vals + 2 * q + 1));
+    sb += Dd<double>(ld_sysd(vals2 + 2 * q), ld_sysd(vals2 + 2 * q + 1));
+  }
+  dst[0] = (T)s.value();
+  dst[1] = (T)sb.value();
+  P.state->ar = tag;
+  if (which == 0) P.state->arb[0] = P.state->arb[1] = tag;
+  if (which == 2) P.state->arb[(slot + 1) & 1] = tag;
+}
+
 constexpr int kWaitGridMax = 256;
 
 int wait_grid(int64_t n_ghost) {
@@ -199,6 +279,15 @@ int peer_allreduce(cgx_csr *A, const T *part, int np, T *dst, CgScalars<T> *st, 
   return CGX_OK;
 }
 
+template <typename T>
+int peer_allreduce2(cgx_csr *A, const T *part_a, const T *part_b, int np, T *dst,
+                    CgScalars<T> *st, int slot, hipStream_t s, int which) {
+  hipLaunchKernelGGL(k_peer_allreduce2<T>, dim3(1), dim3(kBlock), 0, s, part_a, part_b, np, dst,
+                     st, slot, A->peer.dev, which);
+  CGX_HIP(hipGetLastError());
+  return CGX_OK;
+}
+
 template int peer_push<double>(cgx_csr *, const double *, CgScalars<double> *, int, hipStream_t);
 template int peer_push<float>(cgx_csr *, const float *, CgScalars<float> *, int, hipStream_t);
 template int peer_wait<double>(cgx_csr *, double *, CgScalars<double> *, int, hipStream_t);
@@ -209,6 +298,11 @@ template int peer_allreduce<double>(cgx_csr *, const double *, int, double *, Cg
                                     int, hipStream_t, int);
 template int peer_allreduce<float>(cgx_csr *, const float *, int, float *, CgScalars<float> *,
                                    int, hipStream_t, int);
+
+template int peer_allreduce2<double>(cgx_csr *, const double *, const double *, int, double *,
+                                     CgScalars<double> *, int, hipStream_t, int);
+template int peer_allreduce2<float>(cgx_csr *, const float *, const float *, int, float *,
+                                    CgScalars<float> *, int, hipStream_t, int);
 
 int peer_destroy(cgx_csr *A) {
   Peer &pr = A->peer;
@@ -255,7 +349,8 @@ int all_ok(cgx_ctx *ctx, int mine, int *all) {
 }
 
 // the transport against the setup transport: halo of a known vector
-// bit-identical, three all-reduces of known values exact
+// bit-identical, three all-reduces of known values exact, then one paired
+// all-reduce (the preconditioned body's; the val2 area's first use) exact
 template <typename T> int self_test(cgx_csr *A, bool *ok) {
   *ok = false;
   cgx_ctx *ctx = A->ctx;
@@ -267,8 +362,8 @@ template <typename T> int self_test(cgx_csr *A, bool *ok) {
   int rc = CGX_OK;
   hipError_t e = hipMalloc(&v1, next * sizeof(T));
   if (e == hipSuccess) e = hipMalloc(&v2, next * sizeof(T));
-  if (e == hipSuccess) e = hipMalloc(&part, 4 * sizeof(T));
-  if (e == hipSuccess) e = hipMalloc(&res, 4 * sizeof(T));
+  if (e == hipSuccess) e = hipMalloc(&part, 8 * sizeof(T));
+  if (e == hipSuccess) e = hipMalloc(&res, 8 * sizeof(T));
   if (e == hipSuccess) e = hipMemcpyAsync(v1, h.data(), next * sizeof(T), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(v2, h.data(), next * sizeof(T), hipMemcpyHostToDevice, s);
   if (e != hipSuccess) rc = hip_fail(e, "peer self-test (alloc)");
@@ -288,8 +383,26 @@ template <typename T> int self_test(cgx_csr *A, bool *ok) {
       if (e != hipSuccess) rc = hip_fail(e, "peer self-test (all-reduce)");
     }
   }
+  // the paired all-reduce: (rank + 1) + 0.5 and 3 (rank + 1) + 0.25 per rank,
+  // two partial pairs each
+  T want2[2] = {T(0), T(0)};
+  if (!rc) {
+    const T mine[8] = {(T)(ctx->rank + 1), T(0), (T)0.5,  T(0),
+                       (T)(3 * (ctx->rank + 1)), T(0), (T)0.25, T(0)};
+    for (int q = 0; q < ctx->world; ++q) {
+      want2[0] += (T)(q + 1) + (T)0.5;
+      want2[1] += (T)(3 * (q + 1)) + (T)0.25;
+    }
+    e = hipMemcpyAsync(part, mine, 8 * sizeof(T), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) rc = hip_fail(e, "peer self-test (copy)");
+    if (!rc) rc = peer_allreduce2<T>(A, part, part + 4, 2, res + 4, nullptr, 0, s, 0);
+    if (!rc) {
+      e = hipStreamSynchronize(s);  // `mine` is on the stack
+      if (e != hipSuccess) rc = hip_fail(e, "peer self-test (paired all-reduce)");
+    }
+  }
   std::vector<T> g1((size_t)ng + 1), g2((size_t)ng + 1);
-  T got[3];
+  T got[6];
   PeerState ps{};
   if (!rc && ng) {
     e = hipMemcpyAsync(g1.data(), v1 + n, ng * sizeof(T), hipMemcpyDeviceToHost, s);
@@ -297,7 +410,7 @@ template <typename T> int self_test(cgx_csr *A, bool *ok) {
     if (e != hipSuccess) rc = hip_fail(e, "peer self-test (download)");
   }
   if (!rc) {
-    e = hipMemcpyAsync(got, res, 3 * sizeof(T), hipMemcpyDeviceToHost, s);
+    e = hipMemcpyAsync(got, res, 6 * sizeof(T), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
       e = hipMemcpyAsync(&ps, A->peer.state, sizeof(ps), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -306,11 +419,14 @@ template <typename T> int self_test(cgx_csr *A, bool *ok) {
   if (!rc) {
     bool good = ps.fault == 0 && std::memcmp(g1.data(), g2.data(), ng * sizeof(T)) == 0;
     for (int r = 0; r < 3; ++r) good = good && got[r] == want[r];
+    good = good && got[4] == want2[0] && got[5] == want2[1];
     if (!good)
-      set_error("peer transport self-test failed on rank %d (fault %d, halo %s, sums %g/%g)",
+      set_error("peer transport self-test failed on rank %d (fault %d, halo %s, sums %g/%g, "
+                "paired %g/%g %g/%g)",
                 ctx->rank, ps.fault,
                 std::memcmp(g1.data(), g2.data(), ng * sizeof(T)) ? "differs" : "ok",
-                (double)got[0], (double)want[0]);
+                (double)got[0], (double)want[0], (double)got[4], (double)want2[0],
+                (double)got[5], (double)want2[1]);
     *ok = good;
   }
   for (T *p : {v1, v2, part, res})

@@ -127,6 +127,66 @@ __device__ __forceinline__ bool world_sum(Dd<double> mine, unsigned long long t,
   return *ok_lds != 0;
 }
 
+// world_sum for two local sums under one tag (a preconditioned body's r.r and
+// r.z, tag base + 2): the publisher stores the first pair where world_sum
+// does and the second into the val2 area behind the push flags, releases
+// both at system scope, then stores the tag; the hand-off is world_sum's,
+// line for line. thread 0's res_lds[0], res_lds[1] carry the two world
+// values, each summed in rank order and rounded once. false: a spin timed out.
+__device__ __forceinline__ bool world_sum2(Dd<double> mine_a, Dd<double> mine_b,
+                                           unsigned long long t, const PeerDev &P,
+                                           double *res_lds, int *ok_lds) {
+  const int par = (int)(t & 1);
+  if (threadIdx.x < 64) {
+    int claim = 0;
+    if (threadIdx.x == 0)
+      claim = __hip_atomic_load(&P.state->pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < t &&
+              __hip_atomic_fetch_max(&P.state->pub, t, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT) < t;
+    const bool publisher = __shfl(claim, 0, 64) != 0;
+    bool ok = true;
+    if ((int)threadIdx.x < P.world) {
+      if (publisher) {
+        char *box = P.ctl[threadIdx.x];
+        double *val = reinterpret_cast<double *>(box) + 2 * (par * kPeerMax + P.rank);
+        double *val2 =
+            reinterpret_cast<double *>(box + kPeerVal2Off) + 2 * (par * kPeerMax + P.rank);
+        st_sysd(val, mine_a.hi);
+        st_sysd(val + 1, mine_a.lo);
+        st_sysd(val2, mine_b.hi);
+        st_sysd(val2 + 1, mine_b.lo);
+        __threadfence_system();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        st_sys(reinterpret_cast<unsigned long long *>(box + kPeerTagOff) + par * kPeerMax +
+                   P.rank,
+               t);
+      }
+      const auto *tags = reinterpret_cast<const unsigned long long *>(P.ctl[P.rank] + kPeerTagOff);
+      ok = spin_ge(tags + par * kPeerMax + threadIdx.x, t, P.spin_ticks);
+    }
+    ok = __all(ok);
+    if (threadIdx.x == 0) {
+      *ok_lds = ok;
+      if (ok) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // system scope
+        const double *vals =
+            reinterpret_cast<const double *>(P.ctl[P.rank]) + 2 * par * kPeerMax;
+        const double *vals2 =
+            reinterpret_cast<const double *>(P.ctl[P.rank] + kPeerVal2Off) + 2 * par * kPeerMax;
+        Dd<double> sa(0.0), sb(0.0);
+        for (int q = 0; q < P.world; ++q) {
+          sa += Dd<double>(ld_sysd(vals + 2 * q), ld_sysd(vals + 2 * q + 1));
+          sb += Dd<double>(ld_sysd(vals2 + 2 * q), ld_sysd(vals2 + 2 * q + 1));
+        }
+        res_lds[0] = sa.value();
+        res_lds[1] = sb.value();
+      }
+    }
+  }
+  __syncthreads();
+  return *ok_lds != 0;
+}
+
 // Push workgroup wg of nsend x kPushWG: chunk g of send neighbour i's list
 // into its landing buffer, then flag [my rank][g] there with this body's tag
 // (body_tag). Every storing wave drains its stores, then one lane

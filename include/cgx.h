@@ -318,16 +318,30 @@ int cgx_csr_fd_grid(cgx_csr *A, int *fd_grid, int *spmv_grid);
  * stop rule tests the true r.r (Q5), not r.z. With m == 1 every value is the
  * plain solver's, bit for bit. The init is two launches (the plain one, then
  * p = m o r with rz), both under index 0 of cgx_cg_kernel_times.
- * Modes 1 and 3 on a single device, f64 and f32, every SpMV format; mode 0
- * (auto) resolves to 3 while a preconditioner is set. Modes 2, 4, 5, 6, 7
- * and partitioned matrices return CGX_EUNSUPPORTED, from whichever of
- * cgx_cg_set_mode and cgx_cg_set_precond comes second. */
+ * Modes 1 and 3, f64 and f32, every SpMV format, on a single device and on
+ * partitioned matrices (cgx_csr_create_dist) over every transport of the
+ * partitioned solver; mode 0 (auto) resolves to 3 while a preconditioner is
+ * set. Modes 2, 4, 5, 6 and 7 return CGX_EUNSUPPORTED, from whichever of
+ * cgx_cg_set_mode and cgx_cg_set_precond comes second.
+ * Partitioned: m covers the rank's own rows (n_local values); r.z is
+ * all-reduced with r.r as one collective of two values, so a body has the
+ * plain partitioned body's launches and round trips (tags: p.Ap at base + 1,
+ * {r.r, r.z} at base + 2), ranks may mix modes 1 and 3, and cgx_cg_rz,
+ * cgx_cg_rxr and cgx_cg_solve's outputs are the world values, identical on
+ * every rank. cgx_csr_diag_inv and cgx_cg_set_precond (kinds JACOBI and
+ * DIAGONAL) are then COLLECTIVE: every rank makes the same call with the same
+ * kind. The verdict on a bad diagonal is agreed over the setup transport, so
+ * every rank returns the same code and message, with the GLOBAL index; an
+ * argument error or a failed allocation on one rank fails the call on all. */
 enum { CGX_PRECOND_NONE = 0, CGX_PRECOND_JACOBI = 1, CGX_PRECOND_DIAGONAL = 2 };
 /* d_out[i] = 1 / a_ii (entries with col == row summed). Blocking. CGX_EINVAL when a row has no
- * diagonal entry or a_ii is not positive and finite (the message gives the count and the first row). */
+ * diagonal entry or a_ii is not positive and finite (the message gives the count and the first row).
+ * Partitioned A: n_local values, 1 / a_ii of the rank's own rows; collective (above): the count
+ * is the world's and the row the lowest global one, on every rank. */
 int cgx_csr_diag_inv(cgx_csr *A, void *d_out);
 /* kind NONE: d_minv ignored. JACOBI: the solver builds and owns 1/diag(A) (d_minv ignored).
- * DIAGONAL: d_minv = n caller-owned device values, positive and finite (checked, blocking),
+ * DIAGONAL: d_minv = n (partitioned: n_local, the own rows') caller-owned device values,
+ * positive and finite (checked, blocking; partitioned: collectively, the global entry reported),
  * 16-byte aligned (cgx_alloc's are), alive until replaced or the solver is destroyed.
  * Allowed between solves: it ends the current one (cgx_cg_run and cgx_cg_rxr need a new
  * cgx_cg_begin, where it takes effect) and drops the captured graphs. On an error the
