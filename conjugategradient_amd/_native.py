@@ -112,6 +112,12 @@ _SIGS = {
     "cgx_cg_set_precond": (_i32, [_vp, _i32, _vp]),
     "cgx_cg_get_precond": (_i32, [_vp, C.POINTER(_i32)]),
     "cgx_cg_rz": (_i32, [_vp, C.POINTER(_dbl)]),
+    "cgx_cg_solve_batch": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _dbl, _i64, C.POINTER(_i64),
+                                  C.POINTER(_dbl), C.POINTER(_i32)]),
+    "cgx_cg_begin_batch": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _dbl, _i64]),
+    "cgx_cg_run_batch": (_i32, [_vp, _i64, C.POINTER(_i64), C.POINTER(_i32)]),
+    "cgx_cg_set_batch_form": (_i32, [_vp, _i32]),
+    "cgx_cg_batch_info": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "cgx_accuracy": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_dbl)]),
     "cgx_poisson_nnz": (_i64, [_i32, _i32, _i32, _i32, _i64, _i64]),
     "cgx_poisson_fill": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),

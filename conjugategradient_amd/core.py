@@ -380,6 +380,10 @@ class CG:
         self.mode = 0  # cgx_cg_set_mode: 0 auto (5, 4, 6 or 3), 1 three kernels, 2 fused,
         # 3 deferred x, 4 fused + deferred x, 5 persistent body, 6 deferred x with Ap
         # recomputed (lean walk), 7 fused + deferred x with Ap recomputed (tile walk)
+        self.batch_form = 0  # cgx_cg_set_batch_form: 0 auto, 1 fused, 2 sequential
+        self.iterations_batch = None  # extension (solve_batch): loop bodies per column
+        self.final_rxr_batch = None   # r.r after each column's last body
+        self.stopped_batch = None     # 1 stop rule / NaN, 2 cap reached, per column
 
     @classmethod
     def createCG(cls, dtype=np.float64, debug=Debuglevel.None_, device: int = 0) -> "CG":
@@ -499,6 +503,61 @@ class CG:
             check(lib().cgx_cg_rz(self._cg, C.byref(rz)))
             self.final_rz = rz.value
         self.is_solved = True
+
+    MAX_BATCH = 8  # cgx.h: a batch has 1 to 8 right-hand sides
+
+    def solve_batch(self, B, X0=None, improvement: float = 0.0, max_iter: int = -1) -> np.ndarray:
+        """Extension (cgx_cg_solve_batch): k independent solves A x_c = b_c,
+        k = 1..8, the columns of ``B`` (n, k) in any memory order; ``X0`` (same
+        shape) holds the initial guesses (default 0). Returns X (n, k) and sets
+        ``iterations_batch``, ``final_rxr_batch`` and ``stopped_batch``. Every
+        column is the single solve's in mode 1, bit for bit, when the fused
+        form runs (``batch_form``: 0 auto, 1 fused, 2 sequential). ValueError,
+        before any device call, for a wrong row count, k outside 1..8 or an
+        X0 whose shape is not B's."""
+        B = np.asarray(B)
+        n = self.A.N()
+        if B.ndim != 2:
+            raise ValueError(f"B must be a 2-D (n, k) array, got {B.ndim} dimension(s)")
+        if B.shape[0] != n:
+            raise ValueError(f"B has {B.shape[0]} rows, the matrix {n}")
+        k = B.shape[1]
+        if not 1 <= k <= self.MAX_BATCH:
+            raise ValueError(f"a batch has 1 to {self.MAX_BATCH} right-hand sides, got {k}")
+        if X0 is not None:
+            X0 = np.asarray(X0)
+            if X0.shape != B.shape:
+                raise ValueError(f"X0 has shape {X0.shape}, B {B.shape}")
+        if self.A.columns() is None:
+            raise RuntimeError("No Matrix given")
+        # column-major on the device: column c at element c * n
+        dB = DeviceArray(self._queue, n * k, self.dtype).upload(
+            np.asarray(B, dtype=self.dtype).T.ravel())
+        dX = DeviceArray(self._queue, n * k, self.dtype)
+        if X0 is None:
+            dX.fill(0.0)
+        else:
+            dX.upload(np.asarray(X0, dtype=self.dtype).T.ravel())
+        bodies = (C.c_int64 * k)()
+        rxr = (C.c_double * k)()
+        stopped = (C.c_int * k)()
+        cg = self._solver()
+        check(lib().cgx_cg_set_batch_form(cg, int(self.batch_form)))
+        check(lib().cgx_cg_solve_batch(cg, k, dB.ptr, n, dX.ptr, n, float(improvement),
+                                       int(max_iter), bodies, rxr, stopped))
+        self.iterations_batch = np.array(bodies[:], dtype=np.int64)
+        self.final_rxr_batch = np.array(rxr[:], dtype=np.float64)
+        self.stopped_batch = np.array(stopped[:], dtype=np.int32)
+        return np.ascontiguousarray(dX.download().reshape(k, n).T)
+
+    def batch_info(self):
+        """(form in effect: 1 fused or 2 sequential, instantiated width of the
+        fused form's buffers or 0) for ``batch_form`` on this matrix."""
+        cg = self._solver()
+        check(lib().cgx_cg_set_batch_form(cg, int(self.batch_form)))
+        form, width = C.c_int(0), C.c_int(0)
+        check(lib().cgx_cg_batch_info(cg, C.byref(form), C.byref(width)))
+        return form.value, width.value
 
     # -- outputs --------------------------------------------------------
     def accuracy(self) -> float:

@@ -666,6 +666,16 @@ int flush_pending_x(cgx_cg *cg) {
 
 // A cached exec may still be in flight (cgx_cg_run keeps two chunks queued):
 // the stream drains before any is destroyed.
+void drop_batch_graph(cgx_cg *cg) {
+  if (cg->bt.graphs.empty()) return;
+  (void)hipStreamSynchronize(cg->ctx->stream);
+  for (auto &kv : cg->bt.graphs) (void)hipGraphExecDestroy(kv.second);
+  cg->bt.graphs.clear();
+}
+// (The batched solver's chunks go where their own inputs change: the poll
+// interval, a preconditioner, the batch's X / ld / width, and with the solver.
+// A single solve on another x, or a change of the single solver's mode, which
+// the batch body does not depend on, leaves them alone.)
 void drop_graph(cgx_cg *cg) {
   if (cg->graphs.empty()) return;
   (void)hipStreamSynchronize(cg->ctx->stream);
@@ -3482,7 +3492,9 @@ extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
   // the solve in progress ends here; nothing queued may still read the old m
   CGX_HIP(hipStreamSynchronize(s));
   drop_graph(cg);
+  drop_batch_graph(cg);
   cg->begun = false;
+  cg->bt.begun = false;
   if (cg->minv_own) (void)hipFree(cg->minv_own);
   cg->minv_own = own;
   cg->minv = m;
@@ -3528,12 +3540,15 @@ extern "C" int cgx_cg_destroy(cgx_cg *cg) {
   DeviceGuard g(cg->ctx->device);
   (void)hipStreamSynchronize(cg->ctx->stream);
   drop_graph(cg);
+  drop_batch_graph(cg);
   for (auto e : cg->ev_pool) (void)hipEventDestroy(e);
   for (hipEvent_t e : cg->run_ev)
     if (e) (void)hipEventDestroy(e);
   for (void *p : {cg->r, cg->p, cg->p2, cg->Ap, cg->st, cg->ws, cg->pk[0], cg->pk[1], cg->pk[2],
-                  cg->coop_ws, cg->coop_trace, cg->minv_own})
+                  cg->coop_ws, cg->coop_trace, cg->minv_own, cg->bt.r, cg->bt.p, cg->bt.Ap,
+                  cg->bt.st, cg->bt.ws, cg->bt.seq_b, cg->bt.seq_x})
     if (p) (void)hipFree(p);
+  if (cg->bt.h_poll) (void)hipHostFree(cg->bt.h_poll);
   cgx_csr *A = cg->A;
   cgx_ctx *ctx = cg->ctx;
   delete cg;
@@ -3545,7 +3560,10 @@ extern "C" int cgx_cg_destroy(cgx_cg *cg) {
 extern "C" int cgx_cg_config(cgx_cg *cg, int poll_every, int use_graph) {
   CGX_REQUIRE(cg, CGX_EINVAL, "cg is NULL");
   if (poll_every > 0) {
-    if (poll_every != cg->poll_every) drop_graph(cg);
+    if (poll_every != cg->poll_every) {
+      drop_graph(cg);
+      drop_batch_graph(cg);
+    }
     cg->poll_every = poll_every;
   }
   if (use_graph >= 0) cg->use_graph = use_graph != 0;
@@ -3566,6 +3584,7 @@ extern "C" int cgx_cg_begin(cgx_cg *cg, const void *b, void *x, double tol,
   if (max_bodies >= 0) cap = std::min<long long>(cap, std::max<long long>(max_bodies, 1));
   cg->b = b;
   cg->x = x;
+  cg->bt.begun = false;  // a batch in progress ends here
   if (cg->fused)  // p_{-1} = 0 for body 0 of the fused iteration
     CGX_HIP(hipMemsetAsync(cg->p2, 0, (size_t)cg->n * dtype_size(cg->dtype), s));
   if (cg->fdefer)  // mode 4: body 0 reads p_{-1} = P[3] (times beta = 0)
@@ -3865,6 +3884,325 @@ extern "C" int cgx_cg_solve(cgx_cg *cg, const void *b, void *x, double tol, int6
     *rxr_out = view_state(cg, h, (int)(total & 3)).rxr;
   }
   if (bodies_out) *bodies_out = total;
+  return CGX_OK;
+}
+
+// ===========================================================================
+// batched CG: several right-hand sides on one matrix
+// ===========================================================================
+namespace {
+using BSt = CgScalars<double>;
+
+// why the fused form cannot run on this solver (null: it can)
+const char *batch_fused_refusal(const cgx_cg *cg) {
+  if (cg->A->dist) return "the matrix is partitioned (cgx_csr_create_dist)";
+  if (cg->dtype != CGX_F64) return "the solver is f32 (the fused form is f64)";
+  if (cg->precond) return "a preconditioner is set (the fused form is unpreconditioned)";
+  return nullptr;
+}
+// auto: fused for two or more columns where the matrix's production variant
+// is a CSR-stream form (no SELL bit) and the fused form supports the solver,
+// else sequential. One column alone runs the width-2 kernels with a padding
+// column: 72.2 against 40.8 us per body on the G3 stand-in, 56.3 against 33.5
+// (mode 1) on the 26-per-row matrix, while 2, 4 and 8 columns ran 0.94, 0.88
+// and 0.94 of the auto single solve per column on the first and 0.89, 0.73,
+// 0.70 of mode 1 on the second (profiles/batch_bench.log).
+int batch_form_in_effect(const cgx_cg *cg, int nrhs) {
+  if (cg->bt.form) return cg->bt.form;
+  if (nrhs < 2 || batch_fused_refusal(cg)) return 2;
+  return csr_stream_variant(launch_variant(cg->A->dev, cg->dtype)) ? 1 : 2;
+}
+
+int batch_alloc(cgx_cg *cg, int width) {
+  auto &b = cg->bt;
+  hipStream_t s = cg->ctx->stream;
+  if (b.width != width) {
+    CGX_HIP(hipStreamSynchronize(s));
+    drop_batch_graph(cg);
+    for (void **v : {&b.r, &b.p, &b.Ap}) {
+      if (*v) CGX_HIP(hipFree(*v));
+      *v = nullptr;
+    }
+    b.width = 0;
+    const size_t bytes = ((size_t)cg->n + 1) * (size_t)width * sizeof(double);
+    for (void **v : {&b.r, &b.p, &b.Ap}) {
+      CGX_HIP(hipMalloc(v, bytes));
+      CGX_HIP(hipMemsetAsync(*v, 0, bytes, s));
+    }
+    b.width = width;
+  }
+  if (!b.st) {
+    CGX_HIP(hipMalloc(&b.st, kBatchMax * sizeof(BSt)));
+    CGX_HIP(hipMemsetAsync(b.st, 0, kBatchMax * sizeof(BSt), s));
+  }
+  if (!b.ws) CGX_HIP(hipMalloc(&b.ws, sizeof(BatchWs)));
+  if (!b.h_poll) CGX_HIP(hipHostMalloc(&b.h_poll, 2 * kBatchMax * sizeof(BSt)));
+  return CGX_OK;
+}
+
+int enqueue_iter_batch(cgx_cg *cg, int slot) {
+  auto &b = cg->bt;
+  hipStream_t s = cg->ctx->stream;
+  const CsrDev &A = cg->A->dev;
+  auto *st = (BSt *)b.st;
+  auto *ws = (BatchWs *)b.ws;
+  const int npp = Launch<double>::batch_spmv_parts(A, b.width);
+  const int npr = Launch<double>::batch_update_parts(cg->n, b.width);
+  CGX_HIP(Launch<double>::batch_spmv_dot(A, b.width, (const double *)b.p, (double *)b.Ap, st, slot,
+                                         ws, s));
+  CGX_HIP(Launch<double>::batch_update_r(cg->n, b.width, (double *)b.r, (const double *)b.Ap, st,
+                                         slot, ws, npp, s));
+  CGX_HIP(Launch<double>::batch_update_xp(cg->n, b.width, (double *)b.X, b.ldx, (double *)b.p,
+                                          (const double *)b.r, st, slot, ws, npr, s));
+  return CGX_OK;
+}
+
+// the graph of a chunk of `iters` bodies from slot0 (as chunk_graph: cached,
+// else captured when `build`, else null and the chunk is launched eagerly)
+int batch_chunk_graph(cgx_cg *cg, int slot0, int64_t iters, bool build, hipGraphExec_t *out) {
+  auto &b = cg->bt;
+  *out = nullptr;
+  auto it = b.graphs.find({slot0, iters});
+  if (it != b.graphs.end()) {
+    *out = it->second;
+    return CGX_OK;
+  }
+  if (!build) return CGX_OK;
+  if (b.graphs.size() >= 16) drop_batch_graph(cg);
+  hipStream_t s = cg->ctx->stream;
+  CGX_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  int rc = CGX_OK;
+  for (int64_t i = 0; i < iters && rc == CGX_OK; ++i)
+    rc = enqueue_iter_batch(cg, (int)((slot0 + i) & 3));
+  hipGraph_t g = nullptr;
+  hipError_t e = hipStreamEndCapture(s, &g);
+  if (rc) {
+    if (g) (void)hipGraphDestroy(g);
+    return rc;
+  }
+  CGX_HIP(e);
+  hipGraphExec_t ge = nullptr;
+  e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  CGX_HIP(e);
+  if ((e = hipGraphUpload(ge, s)) != hipSuccess) {
+    (void)hipGraphExecDestroy(ge);
+    CGX_HIP(e);
+  }
+  b.graphs[{slot0, iters}] = ge;
+  *out = ge;
+  return CGX_OK;
+}
+
+// the nrhs scalar rings into h (asynchronous)
+int batch_poll(cgx_cg *cg, void *h, hipStream_t s) {
+  CGX_HIP(hipMemcpyAsync(h, cg->bt.st, (size_t)cg->bt.nrhs * sizeof(BSt), hipMemcpyDeviceToHost,
+                         s));
+  return CGX_OK;
+}
+
+int batch_check_args(cgx_cg *cg, int nrhs, const void *B, int64_t ldb, const void *X, int64_t ldx) {
+  CGX_REQUIRE(cg, CGX_EINVAL, "cg is NULL");
+  CGX_REQUIRE(nrhs >= 1 && nrhs <= kBatchMax, CGX_EINVAL,
+              "nrhs = %d: a batch has 1 to %d right-hand sides", nrhs, kBatchMax);
+  CGX_REQUIRE(B && X, CGX_EINVAL, "d_B or d_X is NULL");
+  CGX_REQUIRE(ldb >= cg->n && ldx >= cg->n, CGX_EINVAL,
+              "ldb = %lld, ldx = %lld: a leading dimension is at least n = %lld", (long long)ldb,
+              (long long)ldx, (long long)cg->n);
+  CGX_REQUIRE(!cg->A->dist, CGX_EUNSUPPORTED,
+              "batched CG on a partitioned matrix (cgx_csr_create_dist) is not supported");
+  return CGX_OK;
+}
+}  // namespace
+
+extern "C" int cgx_cg_set_batch_form(cgx_cg *cg, int form) {
+  CGX_REQUIRE(cg, CGX_EINVAL, "cg is NULL");
+  CGX_REQUIRE(form >= 0 && form <= 2, CGX_EINVAL, "batch form %d: 0 auto, 1 fused, 2 sequential",
+              form);
+  if (form != cg->bt.form) cg->bt.last_form = 0;
+  cg->bt.form = form;
+  return CGX_OK;
+}
+
+extern "C" int cgx_cg_batch_info(cgx_cg *cg, int *form_in_effect, int *width) {
+  CGX_REQUIRE(cg, CGX_EINVAL, "cg is NULL");
+  // auto: the last batch's choice, before any the choice for two or more columns
+  const int f = cg->bt.last_form ? cg->bt.last_form : batch_form_in_effect(cg, 2);
+  if (form_in_effect) *form_in_effect = f;
+  if (width) *width = f == 1 ? cg->bt.width : 0;
+  return CGX_OK;
+}
+
+extern "C" int cgx_cg_begin_batch(cgx_cg *cg, int nrhs, const void *d_B, int64_t ldb, void *d_X,
+                                  int64_t ldx, double tol, int64_t max_bodies) {
+  if (int rc = batch_check_args(cg, nrhs, d_B, ldb, d_X, ldx)) return rc;
+  CGX_REQUIRE(batch_form_in_effect(cg, nrhs) == 1, CGX_EUNSUPPORTED,
+              "cgx_cg_begin_batch / cgx_cg_run_batch drive the fused form; the sequential form "
+              "is in effect for %d column(s) (cgx_cg_solve_batch runs it)", nrhs);
+  const char *why = batch_fused_refusal(cg);
+  CGX_REQUIRE(!why, CGX_EUNSUPPORTED, "the fused batch form cannot run: %s", why);
+  DeviceGuard g(cg->ctx->device);
+  hipStream_t s = cg->ctx->stream;
+  auto &b = cg->bt;
+  long long cap = (long long)cg->n + 1;  // as cgx_cg_begin
+  if (max_bodies >= 0) cap = std::min<long long>(cap, std::max<long long>(max_bodies, 1));
+  cg->begun = false;  // a single solve in progress ends here
+  b.begun = false;
+  const int width = Launch<double>::batch_width(nrhs);
+  if (int rc = batch_alloc(cg, width)) return rc;
+  if (b.graph_x != d_X || b.graph_ldx != ldx || b.graph_w != width) drop_batch_graph(cg);
+  b.graph_x = d_X;
+  b.graph_ldx = ldx;
+  b.graph_w = width;
+  b.B = d_B;
+  b.X = d_X;
+  b.ldb = ldb;
+  b.ldx = ldx;
+  b.nrhs = nrhs;
+  CGX_HIP(Launch<double>::batch_init(cg->A->dev, width, nrhs, (const double *)d_X, ldx,
+                                     (const double *)d_B, ldb, (double *)b.r, (double *)b.p,
+                                     (BSt *)b.st, (BatchWs *)b.ws, tol, cap, s));
+  b.slot = 0;
+  b.begun = true;
+  b.last_form = 1;
+  return CGX_OK;
+}
+
+extern "C" int cgx_cg_run_batch(cgx_cg *cg, int64_t bodies, int64_t *bodies_total,
+                                int *all_stopped) {
+  CGX_REQUIRE(cg, CGX_EINVAL, "cg is NULL");
+  CGX_REQUIRE(cg->bt.form != 2, CGX_EUNSUPPORTED,
+              "cgx_cg_begin_batch / cgx_cg_run_batch drive the fused form; the sequential form "
+              "is in effect (cgx_cg_solve_batch runs it)");
+  CGX_REQUIRE(cg->bt.begun, CGX_ESTATE, "cgx_cg_run_batch before cgx_cg_begin_batch");
+  DeviceGuard g(cg->ctx->device);
+  hipStream_t s = cg->ctx->stream;
+  auto &b = cg->bt;
+  const size_t hb = kBatchMax * sizeof(BSt);
+  auto *hbuf = (char *)b.h_poll;
+  for (int k = 0; k < 2; ++k)
+    if (!cg->run_ev[k]) CGX_HIP(hipEventCreateWithFlags(&cg->run_ev[k], hipEventDisableTiming));
+  hipEvent_t *ev = cg->run_ev;
+  struct Pending { int buf; int slot_after; };
+  std::vector<Pending> q;
+  int64_t remaining = std::max<int64_t>(bodies, 0);
+  int chunk_id = 0, rc = CGX_OK, last_buf = -1;
+  bool done = false;
+  auto wait_one = [&]() -> int {
+    const Pending pd = q.front();
+    q.erase(q.begin());
+    CGX_HIP(hipEventSynchronize(ev[pd.buf]));
+    const auto *st = (const BSt *)(hbuf + hb * pd.buf);
+    bool any = false;
+    for (int c = 0; c < b.nrhs; ++c) any = any || st[c].active[pd.slot_after] != 0;
+    if (!any) done = true;
+    last_buf = pd.buf;
+    return CGX_OK;
+  };
+  while (!done && (remaining > 0 || !q.empty())) {
+    if (remaining > 0 && q.size() < 2) {
+      const int64_t chunk = std::min<int64_t>(remaining, cg->poll_every);
+      hipGraphExec_t ge = nullptr;
+      if (cg->use_graph &&
+          (rc = batch_chunk_graph(cg, b.slot, chunk, chunk == cg->poll_every, &ge)))
+        break;
+      if (ge) {
+        CGX_HIP(hipGraphLaunch(ge, s));
+      } else {
+        for (int64_t i = 0; i < chunk && rc == CGX_OK; ++i)
+          rc = enqueue_iter_batch(cg, (b.slot + (int)i) & 3);
+        if (rc) break;
+      }
+      b.slot = (int)((b.slot + chunk) & 3);
+      remaining -= chunk;
+      const int buf = chunk_id++ & 1;
+      if ((rc = batch_poll(cg, hbuf + hb * buf, s))) break;
+      CGX_HIP(hipEventRecord(ev[buf], s));
+      q.push_back(Pending{buf, b.slot});
+      continue;
+    }
+    if ((rc = wait_one())) break;
+  }
+  while (rc == CGX_OK && !q.empty()) rc = wait_one();
+  if (rc) return rc;
+  if (last_buf < 0) {  // no body asked for: the state as it stands
+    if ((rc = batch_poll(cg, hbuf, s))) return rc;
+    last_buf = 0;
+  }
+  CGX_HIP(hipStreamSynchronize(s));
+  const auto *st = (const BSt *)(hbuf + hb * last_buf);
+  bool any = false;
+  for (int c = 0; c < b.nrhs; ++c) {
+    if (bodies_total) bodies_total[c] = st[c].bodies;
+    any = any || st[c].active[b.slot] != 0;
+  }
+  if (all_stopped) *all_stopped = any ? 0 : 1;
+  return CGX_OK;
+}
+
+extern "C" int cgx_cg_solve_batch(cgx_cg *cg, int nrhs, const void *d_B, int64_t ldb, void *d_X,
+                                  int64_t ldx, double tol, int64_t max_bodies,
+                                  int64_t *bodies_out, double *rxr_out, int *stopped_out) {
+  if (int rc = batch_check_args(cg, nrhs, d_B, ldb, d_X, ldx)) return rc;
+  CGX_REQUIRE(bodies_out && rxr_out, CGX_EINVAL, "bodies_out or rxr_out is NULL");
+  int64_t cap = cg->n + 1;
+  if (max_bodies >= 0) cap = std::min<int64_t>(cap, std::max<int64_t>(max_bodies, 1));
+  cg->bt.last_form = batch_form_in_effect(cg, nrhs);
+  if (cg->bt.last_form == 1) {
+    int rc = cgx_cg_begin_batch(cg, nrhs, d_B, ldb, d_X, ldx, tol, max_bodies);
+    if (rc) return rc;
+    int all = 0;
+    if ((rc = cgx_cg_run_batch(cg, cap, bodies_out, &all))) return rc;
+    DeviceGuard g(cg->ctx->device);
+    hipStream_t s = cg->ctx->stream;
+    if ((rc = batch_poll(cg, cg->bt.h_poll, s))) return rc;
+    CGX_HIP(hipStreamSynchronize(s));
+    const auto *st = (const BSt *)cg->bt.h_poll;
+    for (int c = 0; c < nrhs; ++c) {
+      // the rxr after the last body sits in the slot of the first skipped body
+      bodies_out[c] = st[c].bodies;
+      rxr_out[c] = st[c].rxr[st[c].bodies & 3];
+      if (stopped_out) stopped_out[c] = st[c].stopped;
+    }
+    return CGX_OK;
+  }
+  // sequential: the single solve, column by column, in whatever mode the
+  // solver has. A column that is not 16-byte aligned (an odd leading
+  // dimension) goes through an aligned copy: the single kernels read 16-byte
+  // lanes of b's and x's neighbours r and p, and of x itself.
+  DeviceGuard g(cg->ctx->device);
+  hipStream_t s = cg->ctx->stream;
+  const size_t es = dtype_size(cg->dtype), vb = (size_t)cg->n * es;
+  for (int c = 0; c < nrhs; ++c) {
+    const char *bc = (const char *)d_B + (size_t)c * (size_t)ldb * es;
+    char *xc = (char *)d_X + (size_t)c * (size_t)ldx * es;
+    const void *bs = bc;
+    void *xs = xc;
+    if ((uintptr_t)bc & 15) {
+      if (!cg->bt.seq_b) CGX_HIP(hipMalloc(&cg->bt.seq_b, vb + 16));
+      CGX_HIP(hipMemcpyAsync(cg->bt.seq_b, bc, vb, hipMemcpyDeviceToDevice, s));
+      bs = cg->bt.seq_b;
+    }
+    if ((uintptr_t)xc & 15) {
+      if (!cg->bt.seq_x) CGX_HIP(hipMalloc(&cg->bt.seq_x, vb + 16));
+      CGX_HIP(hipMemcpyAsync(cg->bt.seq_x, xc, vb, hipMemcpyDeviceToDevice, s));
+      xs = cg->bt.seq_x;
+    }
+    int rc = cgx_cg_begin(cg, bs, xs, tol, max_bodies);
+    if (rc) return rc;
+    int64_t total = 0;
+    int stopped = 0;
+    if ((rc = cgx_cg_run(cg, cap, &total, &stopped))) return rc;
+    double rxr = 0;
+    if ((rc = cgx_cg_rxr(cg, &rxr))) return rc;
+    if (xs != xc) {
+      CGX_HIP(hipMemcpyAsync(xc, xs, vb, hipMemcpyDeviceToDevice, s));
+      CGX_HIP(hipStreamSynchronize(s));
+    }
+    bodies_out[c] = total;
+    rxr_out[c] = rxr;
+    if (stopped_out) stopped_out[c] = stopped;
+  }
   return CGX_OK;
 }
 

@@ -155,6 +155,17 @@ struct VlClass {
   int pad;
 };
 
+// ---- batched CG (cgx_cg_solve_batch) ---------------------------
+// Up to kBatchMax independent solves on one matrix. Column c has its own
+// CgScalars (an array of kBatchMax) and its own partial sets of the two dots,
+// laid out as RedWs::pap_part / rr_part are (pairs hi, lo per workgroup), so a
+// NaN in one column's sums has no path into another's.
+constexpr int kBatchMax = 8;
+struct BatchWs {
+  double pap[kBatchMax][2 * kMaxGrid];
+  double rr[kBatchMax][2 * kMaxGrid];
+};
+
 struct SellSlice {
   int64_t voff;  // first value of the slice (entries)
   int64_t ioff;  // first index word of the slice (SELL-P: first 16-byte code chunk)
@@ -400,6 +411,24 @@ template <typename T> struct Launch {
                                    const PeerDev *peer = nullptr);
   static hipError_t flush_defer(int64_t n, T *x, T *const P[4], CgScalars<T> *st,
                                 hipStream_t s);
+  // batched CG (f64, one device, the mode-1 body): `width`
+  // (2, 4 or 8, batch_width of the column count) columns per pass over the
+  // CSR arrays; r, p and Ap are interleaved (row i's `width` values adjacent),
+  // X and B the caller's column-major blocks; st: kBatchMax scalar rings.
+  // hipErrorInvalidValue for float and for other widths.
+  static int batch_width(int nrhs);
+  static int batch_spmv_parts(const CsrDev &A, int width);  // the SpMV's grid
+  static int batch_update_parts(int64_t n, int width);      // the vector kernels' grid
+  static hipError_t batch_init(const CsrDev &A, int width, int nrhs, const T *X, int64_t ldx,
+                               const T *B, int64_t ldb, T *r, T *p, CgScalars<T> *st,
+                               BatchWs *ws, T tol, long long cap, hipStream_t s);
+  static hipError_t batch_spmv_dot(const CsrDev &A, int width, const T *p, T *Ap,
+                                   CgScalars<T> *st, int slot, BatchWs *ws, hipStream_t s);
+  static hipError_t batch_update_r(int64_t n, int width, T *r, const T *Ap, CgScalars<T> *st,
+                                   int slot, BatchWs *ws, int np_pap, hipStream_t s);
+  static hipError_t batch_update_xp(int64_t n, int width, T *X, int64_t ldx, T *p, const T *r,
+                                    CgScalars<T> *st, int slot, BatchWs *ws, int np_rr,
+                                    hipStream_t s);
   // diagonal preconditioning (modes 1 and 3 on one device): the
   // three vector kernels with z = m o r formed where r is in registers; m_nt:
   // m read with non-temporal loads (an A/B switch, tools/pcg_bench.py)
@@ -517,6 +546,9 @@ inline int64_t il_bytes(int64_t nnz, int es) {
 
 // the SpMV variant a launch on A uses (dtype: CGX_F64 / CGX_F32)
 int launch_variant(const CsrDev &A, int dtype);
+// a resolved variant that walks the CSR arrays (CSR-stream), not the SELL
+// (bit 2048) or SELL-P (bit 8192) copy
+inline bool csr_stream_variant(int v) { return (v & (2048 | 8192)) == 0; }
 // true when the variant A resolves to (launch_variant) has a k_spmv_dot
 // instantiation: a request that resolves to anything else would only fail
 // at its first launch

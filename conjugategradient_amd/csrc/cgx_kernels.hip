@@ -2695,6 +2695,395 @@ __global__ __launch_bounds__(kBlock, SpmvWaves<V>::w) void k_spmv_dot(CsrArgs A,
   store_part(ws->pap_part, A.part_off + blockIdx.x, e.acc, sm.red);
 }
 
+// ---------------------------------------------------------------------------
+// Batched CG (cgx_cg_solve_batch): W columns per pass over the
+// CSR arrays. A row block's val / col entries are loaded once and stay in
+// registers while the columns go through LDS in groups of CW = min(W, 4)
+// (W = 8: two halves). p, r and Ap are interleaved, row i's W values adjacent,
+// so one gather fetches a row's CW values (16 B / 32 B). The products of a
+// group sit in LDS as prod[entry][CW]; a thread sums one row per column in
+// ascending entry order from 0, k_spmv_dot's order. A row longer than a tile
+// keeps spmv_rows' order (kBlock-strided per-thread sums, block_sum). Columns
+// never share an LDS slot, a sum or a partial; a column whose active flag is
+// off is neither stored nor summed. f64 only.
+// ---------------------------------------------------------------------------
+template <int W> struct BatchGeo {
+  static constexpr int CW = W < 4 ? W : 4;  // columns staged in LDS together
+  static constexpr int H = W / CW;          // groups per row block
+  static constexpr unsigned full = (1u << W) - 1u;
+};
+// (64 KiB less 64 bytes at CW = 4: two workgroups per CU. The staging of the
+// reductions, 8 doubles per column, reuses prod between barriers.)
+template <int CW> struct BatchLds {
+  double prod[(kTile - 2) * CW];
+  __device__ __forceinline__ double *red() { return prod; }
+};
+
+// bit c: column c runs the body in `slot`
+template <int W> __device__ __forceinline__ unsigned batch_active(const CgScalars<double> *st,
+                                                                  int slot) {
+  unsigned m = 0;
+#pragma unroll
+  for (int c = 0; c < W; ++c) m |= st[c].active[slot] != 0 ? 1u << c : 0u;
+  return m;
+}
+
+// CW adjacent doubles at q (16-byte aligned) as 16-byte accesses
+template <int CW> __device__ __forceinline__ void ld_cols(const double *q, double (&g)[CW]) {
+#pragma unroll
+  for (int u = 0; u < CW / 2; ++u) {
+    const double2 v = reinterpret_cast<const double2 *>(q)[u];
+    g[2 * u] = v.x;
+    g[2 * u + 1] = v.y;
+  }
+}
+template <int CW> __device__ __forceinline__ void st_cols(double *q, const double (&g)[CW]) {
+#pragma unroll
+  for (int u = 0; u < CW / 2; ++u)
+    reinterpret_cast<double2 *>(q)[u] = make_double2(g[2 * u], g[2 * u + 1]);
+}
+
+// the gathered vector: interleaved p (the loop), or the caller's column-major
+// X (the init; columns from nrhs on are padding and read as 0)
+template <int W> struct GatherIL {
+  static constexpr int CW = BatchGeo<W>::CW;
+  const double *__restrict__ p;
+  __device__ __forceinline__ void load(int col, int h, double (&g)[CW]) const {
+    ld_cols<CW>(p + (int64_t)col * W + h * CW, g);
+  }
+};
+template <int W> struct GatherCM {
+  static constexpr int CW = BatchGeo<W>::CW;
+  const double *__restrict__ x;
+  int64_t ld;
+  int nrhs;
+  __device__ __forceinline__ void load(int col, int h, double (&g)[CW]) const {
+#pragma unroll
+    for (int u = 0; u < CW; ++u) {
+      const int c = h * CW + u;
+      g[u] = c < nrhs ? x[(int64_t)c * ld + col] : 0.0;
+    }
+  }
+};
+
+// LOADS: 0 plain val / col loads, 1 paired loads (spmv_rows' variant bit 4),
+// 2 paired loads with the 16-bit column deltas (kC16). XCD-contiguous split.
+template <int W, int LOADS, class Epi, class Gather>
+__device__ __forceinline__ void spmv_rows_batch(const CsrArgs &A, const double *__restrict__ val,
+                                                const Gather &x, Epi &epi, unsigned am,
+                                                BatchLds<BatchGeo<W>::CW> &sm) {
+  constexpr int CW = BatchGeo<W>::CW, H = BatchGeo<W>::H;
+  constexpr int E = kTile / kBlock;  // entries per thread
+  constexpr int CAP = kTile - 2;     // TileOf<V>::cap of the full-tile kernels
+  constexpr unsigned gmask = (1u << CW) - 1u;
+  const int t = threadIdx.x;
+  int first, step, end;
+  work_range<1>(A.nrb, first, step, end);
+  for (int bp = first; bp < end; bp += step) {
+    const int b = block_at(A, bp);
+    const int r0 = A.rb[b], nrows = A.rb[b + 1] - r0;
+    const int k0 = A.rbk[b], cnt = A.rbk[b + 1] - k0;
+    if (cnt <= CAP) {
+      const int tr = min(t, max(nrows - 1, 0));
+      const int ra = A.rowptr[r0 + tr] - k0, re = A.rowptr[r0 + tr + 1] - k0;
+      // the block's entries, once for every column: entry e of this thread
+      // belongs at prod[pos[e]] (outside [0, cnt): a clamped or neighbouring
+      // entry, in-range column, product dropped)
+      double v[E];
+      int c[E], pos[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        v[e] = 0.0;
+        c[e] = 0;
+        pos[e] = -1;
+      }
+      if (cnt > 0) {
+        if constexpr (LOADS == 0) {
+#pragma unroll
+          for (int e = 0; e < E; ++e) {
+            const int k = t + e * kBlock, kk = min(k, cnt - 1);
+            v[e] = val[k0 + kk];
+            c[e] = A.col[k0 + kk];
+            pos[e] = k;
+          }
+        } else {
+          using PV = typename PairOf<double>::V;
+          const int ka = k0 & ~1;
+          const int npairs = (k0 + cnt - ka + 1) >> 1;
+          const PV *v2 = reinterpret_cast<const PV *>(val + ka);
+          const Int2 *c2 = reinterpret_cast<const Int2 *>(A.col + ka);
+#pragma unroll
+          for (int u = 0; u < E / 2; ++u) {
+            const int j = min(t + u * kBlock, npairs - 1);
+            const PV vv = v2[j];
+            Int2 cc;
+            if constexpr (LOADS == 2) {
+              // as spmv_rows: a pair's element outside the block is relative
+              // to another block's first row and takes r0
+              typedef short S2 __attribute__((ext_vector_type(2)));
+              const S2 hh = reinterpret_cast<const S2 *>(A.col16 + ka)[j];
+              const int e0 = ka + 2 * j;
+              cc.x = (e0 >= k0 && e0 < k0 + cnt) ? r0 + (int)hh.x : r0;
+              cc.y = (e0 + 1 >= k0 && e0 + 1 < k0 + cnt) ? r0 + (int)hh.y : r0;
+            } else {
+              cc = tail_cols(c2[j], ka + 2 * j, k0 + cnt);
+            }
+            v[2 * u] = vv.x;
+            v[2 * u + 1] = vv.y;
+            c[2 * u] = cc.x;
+            c[2 * u + 1] = cc.y;
+            pos[2 * u] = 2 * (t + u * kBlock) + ka - k0;
+            pos[2 * u + 1] = pos[2 * u] + 1;
+          }
+        }
+      }
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        if (((am >> (h * CW)) & gmask) != 0) {  // uniform: a group with no running column
+          epi.pre(r0 + tr, h);
+          if (cnt > 0) {
+            double g[E][CW];
+#pragma unroll
+            for (int e = 0; e < E; ++e) x.load(c[e], h, g[e]);
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+              if (pos[e] >= 0 && pos[e] < cnt) {
+                double pr[CW];
+#pragma unroll
+                for (int u = 0; u < CW; ++u) pr[u] = v[e] * g[e][u];
+                st_cols<CW>(sm.prod + pos[e] * CW, pr);
+              }
+            }
+          }
+          __syncthreads();
+          if (t < nrows) {
+            double s[CW];
+#pragma unroll
+            for (int u = 0; u < CW; ++u) s[u] = 0.0;
+            for (int j = ra; j < re; ++j) {
+              double q[CW];
+              ld_cols<CW>(sm.prod + j * CW, q);
+#pragma unroll
+              for (int u = 0; u < CW; ++u) s[u] += q[u];
+            }
+            epi.row(r0 + t, h, s);
+          }
+          __syncthreads();
+        }
+      }
+    } else {
+      // one row longer than a tile: spmv_rows' order, per column
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        if (((am >> (h * CW)) & gmask) != 0) {
+          double s[CW];
+#pragma unroll
+          for (int u = 0; u < CW; ++u) s[u] = 0.0;
+          for (int k = t; k < cnt; k += kBlock) {
+            double g[CW];
+            x.load(A.col[k0 + k], h, g);
+            const double vv = val[k0 + k];
+#pragma unroll
+            for (int u = 0; u < CW; ++u) s[u] += vv * g[u];
+          }
+          block_sum<double, CW>(s, sm.red());
+          if (t == 0) {
+            epi.pre(r0, h);
+            epi.row(r0, h, s);
+          }
+          __syncthreads();
+        }
+      }
+    }
+  }
+}
+
+// Each column's workgroup partial of a dot, pairs as store_part lays them out
+// (block_sum_dd's order per column); thread c stores column c's, a column
+// that does not run stores nothing. lds: 8 doubles per column.
+template <int W>
+__device__ __forceinline__ void store_parts_b(double (*part)[2 * kMaxGrid], int i,
+                                              Dd<double> (&v)[W], unsigned am, double *lds) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  constexpr int NW = kBlock / 64;
+#pragma unroll
+  for (int c = 0; c < W; ++c) {
+    const Dd<double> s = wave_sum_dd(v[c]);
+    if (lane == 0) {
+      lds[2 * NW * c + 2 * w] = s.hi;
+      lds[2 * NW * c + 2 * w + 1] = s.lo;
+    }
+  }
+  __syncthreads();
+  const int c = threadIdx.x;
+  if (c < W && ((am >> c) & 1u)) {
+    const double *l = lds + 2 * NW * c;
+    Dd<double> s(l[0], l[1]);
+#pragma unroll
+    for (int k = 1; k < NW; ++k) s += Dd<double>(l[2 * k], l[2 * k + 1]);
+    part[c][2 * i] = s.hi;
+    part[c][2 * i + 1] = s.lo;
+  }
+  __syncthreads();
+}
+
+// The previous kernel's partials of every running column, summed in
+// sum_parts_dd's order (thread t: t, t + 256, ...; waves; workgroup) and
+// handed to every thread; a column that does not run gets 0.
+// lds: 8 doubles per column, bc: 2 per column.
+template <int W>
+__device__ __forceinline__ void sum_parts_b(const double (*part)[2 * kMaxGrid], int np,
+                                            unsigned am, Dd<double> (&out)[W], double *lds,
+                                            double *bc) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  constexpr int NW = kBlock / 64;
+#pragma unroll
+  for (int c = 0; c < W; ++c) {
+    Dd<double> v(0.0);
+    if ((am >> c) & 1u)
+      for (int i = threadIdx.x; i < np; i += kBlock) v += load_part(part[c], i);
+    v = wave_sum_dd(v);
+    if (lane == 0) {
+      lds[2 * NW * c + 2 * w] = v.hi;
+      lds[2 * NW * c + 2 * w + 1] = v.lo;
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < W) {
+    const double *l = lds + 2 * NW * threadIdx.x;
+    Dd<double> s(l[0], l[1]);
+#pragma unroll
+    for (int k = 1; k < NW; ++k) s += Dd<double>(l[2 * k], l[2 * k + 1]);
+    bc[2 * threadIdx.x] = s.hi;
+    bc[2 * threadIdx.x + 1] = s.lo;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < W; ++c) out[c] = Dd<double>(bc[2 * c], bc[2 * c + 1]);
+  __syncthreads();  // lds and bc are free again
+}
+
+template <int W> struct EpiDotB {  // EpiDot per column: Ap = A p; p.Ap
+  static constexpr int CW = BatchGeo<W>::CW;
+  double *__restrict__ Ap;
+  const double *__restrict__ p;
+  unsigned am;
+  Dd<double> acc[W];
+  double pv[CW];
+  __device__ __forceinline__ void pre(int i, int h) {
+    ld_cols<CW>(p + (int64_t)i * W + h * CW, pv);
+  }
+  __device__ __forceinline__ void row(int i, int h, const double (&s)[CW]) {
+    constexpr unsigned gmask = (1u << CW) - 1u;
+    double *q = Ap + (int64_t)i * W + h * CW;
+    const unsigned g = (am >> (h * CW)) & gmask;
+    if (g == gmask) {
+      st_cols<CW>(q, s);
+    } else {
+#pragma unroll
+      for (int u = 0; u < CW; ++u)
+        if ((g >> u) & 1u) q[u] = s[u];
+    }
+#pragma unroll
+    for (int u = 0; u < CW; ++u)
+      if ((g >> u) & 1u) acc[h * CW + u] += s[u] * pv[u];
+  }
+};
+template <int W> struct EpiInitB {  // EpiInit per column; padding columns: r = p = 0
+  static constexpr int CW = BatchGeo<W>::CW;
+  const double *__restrict__ B;
+  int64_t ldb;
+  int nrhs;
+  double *__restrict__ r;
+  double *__restrict__ p;
+  Dd<double> acc[W];
+  double bv[CW];
+  __device__ __forceinline__ void pre(int i, int h) {
+#pragma unroll
+    for (int u = 0; u < CW; ++u) {
+      const int c = h * CW + u;
+      bv[u] = c < nrhs ? B[(int64_t)c * ldb + i] : 0.0;
+    }
+  }
+  __device__ __forceinline__ void row(int i, int h, const double (&s)[CW]) {
+    double ri[CW];
+#pragma unroll
+    for (int u = 0; u < CW; ++u) {
+      ri[u] = h * CW + u < nrhs ? bv[u] - s[u] : 0.0;
+      if (h * CW + u < nrhs) acc[h * CW + u] += ri[u] * ri[u];
+    }
+    st_cols<CW>(r + (int64_t)i * W + h * CW, ri);
+    st_cols<CW>(p + (int64_t)i * W + h * CW, ri);
+  }
+};
+
+// k_spmv_dot for W columns: Ap = A p and each running column's p.Ap partials
+template <int W, int LOADS>
+__global__ __launch_bounds__(kBlock) void k_spmv_dot_b(CsrArgs A, const double *__restrict__ val,
+                                                       const double *__restrict__ p,
+                                                       double *__restrict__ Ap,
+                                                       CgScalars<double> *st, int slot,
+                                                       BatchWs *ws) {
+  const unsigned am = batch_active<W>(st, slot);
+  if (!am) return;
+  __shared__ BatchLds<BatchGeo<W>::CW> sm;
+  EpiDotB<W> e;
+  e.Ap = Ap;
+  e.p = p;
+  e.am = am;
+#pragma unroll
+  for (int c = 0; c < W; ++c) e.acc[c] = Dd<double>(0.0);
+  spmv_rows_batch<W, LOADS>(A, val, GatherIL<W>{p}, e, am, sm);
+  store_parts_b<W>(ws->pap, blockIdx.x, e.acc, am, sm.red());
+}
+
+// k_cg_init for W columns, first of two launches: r = b - A x, p = r and the
+// r.r partials of the nrhs columns (no ticket: k_cg_init_settle_b sums them)
+template <int W>
+__global__ __launch_bounds__(kBlock) void k_cg_init_b(CsrArgs A, const double *__restrict__ val,
+                                                      const double *__restrict__ X, int64_t ldx,
+                                                      const double *__restrict__ B, int64_t ldb,
+                                                      int nrhs, double *__restrict__ r,
+                                                      double *__restrict__ p, BatchWs *ws) {
+  __shared__ BatchLds<BatchGeo<W>::CW> sm;
+  EpiInitB<W> e;
+  e.B = B;
+  e.ldb = ldb;
+  e.nrhs = nrhs;
+  e.r = r;
+  e.p = p;
+#pragma unroll
+  for (int c = 0; c < W; ++c) e.acc[c] = Dd<double>(0.0);
+  // every group runs: the padding columns' r and p are written too
+  spmv_rows_batch<W, 0>(A, val, GatherCM<W>{X, ldx, nrhs}, e, BatchGeo<W>::full, sm);
+  store_parts_b<W>(ws->rr, blockIdx.x, e.acc, (1u << nrhs) - 1u, sm.red());
+}
+// ... second: workgroup c sets column c's scalars as k_cg_init does (rxr[0]
+// from the partials); a padding column never runs
+__global__ __launch_bounds__(kBlock) void k_cg_init_settle_b(CgScalars<double> *stb, BatchWs *ws,
+                                                             int np, int nrhs, double tol,
+                                                             long long cap) {
+  __shared__ double red[8];
+  const int c = blockIdx.x;
+  CgScalars<double> *st = stb + c;
+  const bool real = c < nrhs;  // uniform
+  double rr = 0.0;
+  if (real) rr = sum_parts(ws->rr[c], np, red);
+  if (threadIdx.x == 0) {
+    st->rxr[0] = rr;
+    st->pAp[0] = st->rr[0] = 0.0;
+    st->tol = tol;
+    st->active[0] = real ? 1 : 0;
+    st->active[1] = st->active[2] = st->active[3] = 0;
+    st->xpend[0] = st->xpend[1] = st->xpend[2] = st->xpend[3] = 0;
+    for (int t = 0; t < 4; ++t) st->ran[t] = st->skip[t] = 0;
+    st->bodies = 0;
+    st->cap = cap;
+    st->stopped = real ? 0 : 2;
+    st->tail_fault = 0;
+  }
+}
+
 // k_spmv_dot in the lean stencil walk (kVL): the same epilogue and partials
 // the lean walk's LDS copy of the value dictionary and the templates (a
 // uniform branch: every thread of the workgroup takes it or none)
@@ -4314,6 +4703,132 @@ __global__ __launch_bounds__(kBlock) void k_update_xp_peer(int64_t n, T *__restr
                                                            RedWs<T> *ws, int np_rr, int rev,
                                                            PeerDev P) {
   update_xp_body<T, true>(n, x, p, r, st, slot, ws, np_rr, rev, &P);
+}
+
+// Batched CG: k_update_r and k_update_xp over the interleaved
+// r, p and Ap (a thread takes a row's W values), each column with its own
+// alpha and beta from its own ring. A column that does not run is not loaded
+// from x, not stored and not summed; the others keep the single kernels'
+// per-element expressions.
+template <int W>
+__device__ __forceinline__ void st_cols_masked(double *q, const double (&v)[W], unsigned am) {
+  if (am == BatchGeo<W>::full) {
+    st_cols<W>(q, v);
+  } else {
+#pragma unroll
+    for (int c = 0; c < W; ++c)
+      if ((am >> c) & 1u) q[c] = v[c];
+  }
+}
+template <int W>
+__global__ __launch_bounds__(kBlock) void k_update_r_b(int64_t n, double *r,
+                                                       const double *__restrict__ Ap,
+                                                       CgScalars<double> *st, int slot,
+                                                       BatchWs *ws, int np_pap) {
+  const unsigned am = batch_active<W>(st, slot);
+  if (!am) return;
+  __shared__ double red[2 * (kBlock / 64) * kBatchMax];
+  __shared__ double bc[2 * kBatchMax];
+  Dd<double> pd[W];
+  sum_parts_b<W>(ws->pap, np_pap, am, pd, red, bc);
+  double alpha[W];
+#pragma unroll
+  for (int c = 0; c < W; ++c) {
+    alpha[c] = 0.0;
+    if ((am >> c) & 1u) {
+      const double pAp = pd[c].value();
+      alpha[c] = st[c].rxr[slot] / pAp;
+      if (blockIdx.x == 0 && threadIdx.x == 0) {  // the record, as k_update_r
+        st[c].pAp[slot] = pAp;
+        st[c].alpha[slot] = alpha[c];
+        st[c].skip[slot] = 0;
+      }
+    }
+  }
+  Dd<double> acc[W];
+#pragma unroll
+  for (int c = 0; c < W; ++c) acc[c] = Dd<double>(0.0);
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    double rv[W], av[W];
+    ld_cols<W>(r + i * W, rv);
+    ld_cols<W>(Ap + i * W, av);
+#pragma unroll
+    for (int c = 0; c < W; ++c) {
+      if ((am >> c) & 1u) {
+        rv[c] = rv[c] - alpha[c] * av[c];
+        acc[c] += rv[c] * rv[c];
+      }
+    }
+    st_cols_masked<W>(r + i * W, rv, am);
+  }
+  store_parts_b<W>(ws->rr, blockIdx.x, acc, am, red);
+}
+
+template <int W>
+__global__ __launch_bounds__(kBlock) void k_update_xp_b(int64_t n, double *X, int64_t ldx,
+                                                        double *p, const double *__restrict__ r,
+                                                        CgScalars<double> *st, int slot,
+                                                        BatchWs *ws, int np_rr) {
+  const int nxt = (slot + 1) & 3;
+  const unsigned am = batch_active<W>(st, slot);
+  const bool rec = blockIdx.x == 0 && threadIdx.x == 0;
+  if (!am) {
+    if (rec) {
+#pragma unroll
+      for (int c = 0; c < W; ++c) st[c].active[nxt] = 0;
+    }
+    return;
+  }
+  __shared__ double red[2 * (kBlock / 64) * kBatchMax];
+  __shared__ double bc[2 * kBatchMax];
+  Dd<double> rd[W];
+  sum_parts_b<W>(ws->rr, np_rr, am, rd, red, bc);
+  double alpha[W], beta[W], rxr[W], rr[W];
+#pragma unroll
+  for (int c = 0; c < W; ++c) {
+    alpha[c] = beta[c] = rxr[c] = rr[c] = 0.0;
+    if ((am >> c) & 1u) {
+      rxr[c] = st[c].rxr[slot];
+      alpha[c] = rxr[c] / st[c].pAp[slot];
+      rr[c] = rd[c].value();
+      beta[c] = rr[c] / rxr[c];
+    }
+  }
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    double pv[W], rv[W], xv[W];
+    ld_cols<W>(p + i * W, pv);
+    ld_cols<W>(r + i * W, rv);
+#pragma unroll
+    for (int c = 0; c < W; ++c)
+      if ((am >> c) & 1u) xv[c] = X[c * ldx + i];
+#pragma unroll
+    for (int c = 0; c < W; ++c) {
+      if ((am >> c) & 1u) {
+        X[c * ldx + i] = xv[c] + alpha[c] * pv[c];
+        pv[c] = rv[c] + beta[c] * pv[c];
+      }
+    }
+    st_cols_masked<W>(p + i * W, pv, am);
+  }
+  if (rec) {  // each column's record and stop rule, as k_update_xp
+#pragma unroll
+    for (int c = 0; c < W; ++c) {
+      if (!((am >> c) & 1u)) {
+        st[c].active[nxt] = 0;
+        continue;
+      }
+      st[c].rr[slot] = rr[c];
+      const long long m = st[c].bodies + 1;
+      st[c].bodies = m;
+      const bool cond = isnan(rxr[c]) || sqrt(rxr[c]) <= st[c].tol;
+      const bool cont = !cond && m < st[c].cap;
+      st[c].active[nxt] = cont ? 1 : 0;
+      st[c].rxr[nxt] = rr[c];
+      st[c].stopped = cond ? 1 : (cont ? 0 : 2);
+    }
+  }
 }
 
 // *res += x.y (dot_product_trivial / norm: accumulate, Q4)
@@ -6431,6 +6946,126 @@ hipError_t Launch<T>::update_xp(int64_t n, T *x, T *p, const T *r, CgScalars<T> 
     CGX_LAUNCH(k_update_xp_peer<T>, grid_elems(n, kGridUpdateP), n, x, p, r, st, slot, ws, np_rr,
                rev, *peer);
   CGX_LAUNCH(k_update_xp<T>, grid_elems(n, kGridUpdateP), n, x, p, r, st, slot, ws, np_rr, rev);
+}
+
+// ---- batched CG ----------------------------------------------
+// Widths 2, 4 and 8 are built; other column counts run the next width with
+// padding columns that never become active.
+template <typename T> int Launch<T>::batch_width(int nrhs) {
+  return nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : 8;
+}
+// the loads of k_spmv_dot_b: paired where spmv_variant allows them, the
+// 16-bit deltas where the matrix's variant reads them
+static int batch_loads(const CsrDev &A) {
+  if (((uintptr_t)A.val % 16) || ((uintptr_t)A.col % 8) || A.nnz < 2) return 0;
+  return (A.col16 && (A.variant & kC16)) ? 2 : 1;
+}
+static const void *batch_spmv_kernel(int width, int loads) {
+#define CGX_KB(WW, LL) \
+  if (width == WW && loads == LL) return reinterpret_cast<const void *>(&k_spmv_dot_b<WW, LL>);
+  CGX_KB(2, 0) CGX_KB(2, 1) CGX_KB(2, 2) CGX_KB(4, 0) CGX_KB(4, 1) CGX_KB(4, 2)
+  CGX_KB(8, 0) CGX_KB(8, 1) CGX_KB(8, 2)
+#undef CGX_KB
+  return nullptr;
+}
+// a persistent grid of at most the resident workgroups (64 KiB of LDS at
+// widths 4 and 8: two per CU), a multiple of 8 for the XCD-contiguous split
+template <typename T> int Launch<T>::batch_spmv_parts(const CsrDev &A, int width) {
+  static std::mutex mu;
+  static std::map<std::pair<int, int>, int> cache;  // (device, width) -> workgroups
+  int dev = 0, res = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find({dev, width});
+    if (it != cache.end()) {
+      res = it->second;
+    } else {
+      int nb = 0, cus = 0;
+      const void *k = batch_spmv_kernel(width, 1);
+      if (k && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kBlock, 0) == hipSuccess &&
+          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
+        res = nb * cus;
+      cache[{dev, width}] = res;
+    }
+  }
+  int g = grid_rows(A.nrb);
+  if (res > 0 && res < g) g = res;
+  return g >= 8 ? g & ~7 : g;
+}
+template <typename T> int Launch<T>::batch_update_parts(int64_t n, int width) {
+  return grid_elems(n * width, kGridUpdateP);
+}
+template <typename T>
+hipError_t Launch<T>::batch_init(const CsrDev &A, int width, int nrhs, const T *X, int64_t ldx,
+                                 const T *B, int64_t ldb, T *r, T *p, CgScalars<T> *st,
+                                 BatchWs *ws, T tol, long long cap, hipStream_t s) {
+  if constexpr (std::is_same<T, double>::value) {
+    const int g = batch_spmv_parts(A, width);
+    const CsrArgs a = args(A);
+    const double *val = (const double *)A.val;
+#define CGX_BI(WW)                                                                          \
+  case WW:                                                                                  \
+    CGX_GGL(k_cg_init_b<WW>, dim3(g), dim3(kBlock), 0, s, a, val, X, ldx, B, ldb, nrhs, r, p, \
+            ws);                                                                            \
+    break;
+    switch (width) {
+      CGX_BI(2) CGX_BI(4) CGX_BI(8)
+      default: return hipErrorInvalidValue;
+    }
+#undef CGX_BI
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    CGX_GGL(k_cg_init_settle_b, dim3(width), dim3(kBlock), 0, s, st, ws, g, nrhs, tol, cap);
+    return hipGetLastError();
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
+template <typename T>
+hipError_t Launch<T>::batch_spmv_dot(const CsrDev &A, int width, const T *p, T *Ap,
+                                     CgScalars<T> *st, int slot, BatchWs *ws, hipStream_t s) {
+  if constexpr (std::is_same<T, double>::value) {
+    const void *k = batch_spmv_kernel(width, batch_loads(A));
+    if (!k) return hipErrorInvalidValue;
+    CsrArgs a = args(A);
+    const double *val = (const double *)A.val;
+    void *argv[] = {&a, &val, &p, &Ap, &st, &slot, &ws};
+    return cgx_lk(k, dim3(batch_spmv_parts(A, width)), dim3(kBlock), argv, 0, s);
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
+template <typename T>
+hipError_t Launch<T>::batch_update_r(int64_t n, int width, T *r, const T *Ap, CgScalars<T> *st,
+                                     int slot, BatchWs *ws, int np_pap, hipStream_t s) {
+  if constexpr (std::is_same<T, double>::value) {
+    const int g = batch_update_parts(n, width);
+    switch (width) {
+      case 2: CGX_LAUNCH(k_update_r_b<2>, g, n, r, Ap, st, slot, ws, np_pap);
+      case 4: CGX_LAUNCH(k_update_r_b<4>, g, n, r, Ap, st, slot, ws, np_pap);
+      case 8: CGX_LAUNCH(k_update_r_b<8>, g, n, r, Ap, st, slot, ws, np_pap);
+      default: return hipErrorInvalidValue;
+    }
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
+template <typename T>
+hipError_t Launch<T>::batch_update_xp(int64_t n, int width, T *X, int64_t ldx, T *p, const T *r,
+                                      CgScalars<T> *st, int slot, BatchWs *ws, int np_rr,
+                                      hipStream_t s) {
+  if constexpr (std::is_same<T, double>::value) {
+    const int g = batch_update_parts(n, width);
+    switch (width) {
+      case 2: CGX_LAUNCH(k_update_xp_b<2>, g, n, X, ldx, p, r, st, slot, ws, np_rr);
+      case 4: CGX_LAUNCH(k_update_xp_b<4>, g, n, X, ldx, p, r, st, slot, ws, np_rr);
+      case 8: CGX_LAUNCH(k_update_xp_b<8>, g, n, X, ldx, p, r, st, slot, ws, np_rr);
+      default: return hipErrorInvalidValue;
+    }
+  } else {
+    return hipErrorInvalidValue;
+  }
 }
 template <typename T>
 hipError_t Launch<T>::update_p_defer(int64_t n, T *x, const T *p, T *pn, T *const P[4],

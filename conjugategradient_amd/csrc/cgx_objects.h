@@ -266,6 +266,31 @@ struct cgx_cg {
   // cgx_cg_run's two poll events, created once (an event create and destroy
   // per run sat inside every caller's timed region)
   hipEvent_t run_ev[2] = {nullptr, nullptr};
+  // batched CG (cgx_cg_solve_batch). The fused form's buffers
+  // are allocated on first use for the width in use and freed with the solver.
+  struct Batch {
+    int form = 0;             // cgx_cg_set_batch_form: 0 auto, 1 fused, 2 sequential
+    int last_form = 0;        // the form the last batch call took (0: none since the form was set)
+    int width = 0, nrhs = 0;  // the instantiated width the buffers hold, the columns begun
+    void *r = nullptr, *p = nullptr, *Ap = nullptr;  // interleaved, (n + 1) x width
+    void *st = nullptr;       // cgx::CgScalars<double>[kBatchMax]
+    void *ws = nullptr;       // cgx::BatchWs
+    void *h_poll = nullptr;   // pinned: two copies of st (cgx_cg_run_batch's polls)
+    // the sequential form's staging of a column that is not 16-byte aligned
+    // (an odd leading dimension; the single kernels read 16-byte lanes)
+    void *seq_b = nullptr, *seq_x = nullptr;
+    const void *B = nullptr;
+    void *X = nullptr;
+    int64_t ldb = 0, ldx = 0;
+    int slot = 0;
+    bool begun = false;
+    // captured chunks keyed by (first slot, bodies), for X = graph_x at
+    // leading dimension graph_ldx and width graph_w
+    std::map<std::pair<int, int64_t>, hipGraphExec_t> graphs;
+    void *graph_x = nullptr;
+    int64_t graph_ldx = 0;
+    int graph_w = 0;
+  } bt;
   // kernel timing
   bool timing = false;
   std::vector<hipEvent_t> ev_pool;

@@ -217,6 +217,57 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
     if (_solver) apply_precond(_solver.get());
   }
   Preconditioner preconditioner() const { return _precond; }
+  /**
+   * Batched solve (cgx_cg_solve_batch of cgx.h): B.size() = k independent
+   * right-hand sides, 1 <= k <= 8, on the matrix in place. X[c] holds column
+   * c's initial guess on entry (an unallocated Vector: zero) and its solution
+   * on return. The vectors are copied to and from column-major device
+   * storage. Every column is the single solve's in mode 1, bit for bit, where
+   * the fused form runs (setBatchForm: 0 auto, 1 fused, 2 sequential).
+   * @throw std::invalid_argument for k outside 1..8, X.size() != k or a
+   *        vector whose length is not N
+   */
+  void solveBatch(const std::vector<Vector> &B, std::vector<Vector> &X,
+                  DT improvement = static_cast<DT>(0)) {
+    const std::size_t k = B.size(), n = static_cast<std::size_t>(A.N());
+    if (k < 1 || k > 8) throw std::invalid_argument("solveBatch: 1 to 8 right-hand sides");
+    if (X.size() != k) throw std::invalid_argument("solveBatch: X.size() != B.size()");
+    if (this->A.columns().get() == nullptr) throw std::runtime_error("No Matrix given");
+    for (std::size_t c = 0; c < k; ++c) {
+      Vector &bc = const_cast<Vector &>(B[c]);  // the accessors are not const
+      if (X[c].ptr() == nullptr) X[c].init_empty(n);
+      if (bc.ptr() == nullptr || static_cast<std::size_t>(bc.N()) != n ||
+          static_cast<std::size_t>(X[c].N()) != n)
+        throw std::invalid_argument("solveBatch: a vector's length is not N");
+    }
+    Vector Bd(_queue, n * k), Xd(_queue, n * k);
+    for (std::size_t c = 0; c < k; ++c) {
+      Vector &bc = const_cast<Vector &>(B[c]);
+      check(cgx_d2d(_queue.native(), Bd.ptr() + c * n, bc.ptr(), n * sizeof(DT)), "solveBatch");
+      check(cgx_d2d(_queue.native(), Xd.ptr() + c * n, X[c].ptr(), n * sizeof(DT)), "solveBatch");
+    }
+    cgx_cg *s = solver();
+    check(cgx_cg_set_batch_form(s, _batch_form), "setBatchForm");
+    std::vector<int64_t> bodies(k);
+    std::vector<double> rxr(k);
+    std::vector<int> stopped(k);
+    check(cgx_cg_solve_batch(s, static_cast<int>(k), Bd.ptr(), static_cast<int64_t>(n), Xd.ptr(),
+                             static_cast<int64_t>(n), (double)improvement, _max_iterations,
+                             bodies.data(), rxr.data(), stopped.data()),
+          "solveBatch");
+    for (std::size_t c = 0; c < k; ++c)
+      check(cgx_d2d(_queue.native(), X[c].ptr(), Xd.ptr() + c * n, n * sizeof(DT)), "solveBatch");
+    check(cgx_sync(_queue.native()), "solveBatch");
+    _batch_iterations.assign(bodies.begin(), bodies.end());
+    _batch_rxr = rxr;
+    _batch_stopped = stopped;
+  }
+  /** 0 auto, 1 fused, 2 sequential (cgx_cg_set_batch_form) */
+  void setBatchForm(int form) { _batch_form = form; }
+  /** per column of the last solveBatch: loop bodies, r.r after the last body, stop code */
+  const std::vector<long long> &batchIterations() const { return _batch_iterations; }
+  const std::vector<double> &batchFinalResidualSquared() const { return _batch_rxr; }
+  const std::vector<int> &batchStopped() const { return _batch_stopped; }
 
  private:
   void executeQueue() {
@@ -267,6 +318,10 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
   long long _max_iterations = -1;
   Preconditioner _precond = Preconditioner::None;
   Vector _minv{_queue};
+  int _batch_form = 0;
+  std::vector<long long> _batch_iterations;
+  std::vector<double> _batch_rxr;
+  std::vector<int> _batch_stopped;
 };
 
 };  // namespace CGSolver

@@ -351,6 +351,73 @@ int cgx_cg_get_precond(cgx_cg *cg, int *kind);
 /* r.z after the last body (blocking); CGX_ESTATE without a preconditioner */
 int cgx_cg_rz(cgx_cg *cg, double *rz);
 
+/* ---- batched CG: several right-hand sides on one matrix (replaces nothing in
+ * the reference, whose solve takes one b) ----------------------
+ * A batch is nrhs (1..8) INDEPENDENT solves A x_c = b_c: column c has its own
+ * scalar ring, stop rule (Q5), cap min(N + 1, max_bodies) and stop code, and
+ * stops on its own; the batch ends when every column has. Column c's x, body
+ * count, stop code and final r.r are, bit for bit, those of cgx_cg_solve in
+ * mode 1 on the same matrix, b_c, initial x_c, tol and cap (the double-length
+ * dots make the sums independent of how rows are dealt to threads). A NaN or
+ * Inf in one column stops that column by the NaN rule and reaches no other.
+ * d_B and d_X are column-major: column c starts at element c * ld, ld >= n;
+ * elements [n, ld) of a column are neither read nor written. d_X holds the
+ * initial guesses and receives the results.
+ * Two forms (cgx_cg_set_batch_form):
+ *   fused (1): one pass over the CSR arrays per body serves every column
+ *     (three launches per body for the whole batch: the batched SpMV with each
+ *     column's p.Ap, then the r and the x / p updates with each column's own
+ *     alpha and beta). p, r and Ap are kept interleaved (a row's columns
+ *     adjacent), so a gathered row is one 16 / 32-byte access per 2 / 4
+ *     columns. Widths 2, 4 and 8 are built; another nrhs runs the next width
+ *     with padding columns that never become active. Any single-device f64
+ *     matrix (it walks the CSR arrays, whatever the matrix's SpMV format);
+ *     CGX_EUNSUPPORTED with a preconditioner set, on an f32 solver and on a
+ *     partitioned matrix (the message names the reason).
+ *   sequential (2): cgx_cg_solve's steps once per column, in whatever mode
+ *     the solver has, a preconditioner and f32 included (a column that is not
+ *     16-byte aligned, i.e. an odd ld, is solved through an aligned copy).
+ *   auto (0, the default): fused for nrhs >= 2 where the matrix's production
+ *     SpMV variant is a CSR-stream form and the fused form supports the
+ *     solver, else sequential. Measured with tools/batch_bench.py on an
+ *     MI355X (400 bodies, graph replay, three interleaved rounds, medians;
+ *     profiles/batch_bench.log), µs per body per column, fused against the
+ *     auto-mode single solve: G3 stand-in (4.8 entries per row) 38.4 / 35.9 /
+ *     38.3 against 40.8 at 2 / 4 / 8 columns, every fused round below every
+ *     single round; irregular_spd(400,000, mean_deg 26) 29.9 / 24.4 / 23.4
+ *     against 33.5 in mode 1 (its auto mode, 5, ran 277). One column alone
+ *     runs width 2 with a padding column and loses, 72.2 against 40.8 and
+ *     56.3 against 33.5, so auto keeps nrhs = 1 sequential.
+ * Partitioned matrices return CGX_EUNSUPPORTED in both forms.
+ * A batch call ends a single solve in progress (cgx_cg_run then needs a new
+ * cgx_cg_begin) and cgx_cg_begin ends a batch in progress. The batch's
+ * buffers are allocated on first use and freed by cgx_cg_destroy.
+ * cgx_cg_solve_batch: blocking. bodies_out[nrhs], rxr_out[nrhs] (the r.r
+ * after each column's last body), stopped_out[nrhs] (may be NULL; 1 stop rule
+ * or NaN, 2 cap reached). CGX_EINVAL for nrhs outside 1..8, ld < n or a NULL
+ * pointer. */
+int cgx_cg_solve_batch(cgx_cg *cg, int nrhs, const void *d_B, int64_t ldb, void *d_X, int64_t ldx,
+                       double tol, int64_t max_bodies, int64_t *bodies_out, double *rxr_out,
+                       int *stopped_out);
+/* The split form of the FUSED batch (CGX_EUNSUPPORTED while the sequential
+ * form is in effect), as cgx_cg_begin / cgx_cg_run: init of every column,
+ * then up to `bodies` more bodies, captured as hipGraphs in chunks of the
+ * poll interval (cgx_cg_config); the host's poll copies the nrhs scalar
+ * rings. bodies_total[nrhs]: each column's bodies so far; *all_stopped: 1
+ * when no column is active any more. A stopped column's x, r and p are not
+ * touched by later bodies. */
+int cgx_cg_begin_batch(cgx_cg *cg, int nrhs, const void *d_B, int64_t ldb, void *d_X, int64_t ldx,
+                       double tol, int64_t max_bodies);
+int cgx_cg_run_batch(cgx_cg *cg, int64_t bodies, int64_t *bodies_total, int *all_stopped);
+/* form: 0 auto, 1 fused, 2 sequential (above); takes effect at the next batch call. */
+int cgx_cg_set_batch_form(cgx_cg *cg, int form);
+/* *form_in_effect: 1 or 2: the form the last batch call took or, before any
+ * since the form was set, auto resolved for nrhs >= 2 against the matrix and
+ * the solver as they are now; *width: the instantiated width of the fused
+ * form's buffers (2, 4 or 8; 0 before its first batch and while sequential is
+ * in effect). */
+int cgx_cg_batch_info(cgx_cg *cg, int *form_in_effect, int *width);
+
 /* CG::accuracy (CG.hpp:463-515): blocking; |sum (b-Ax)^2 / sum x^2|. */
 int cgx_accuracy(cgx_ctx *ctx, cgx_csr *A, const void *d_b, const void *d_x,
                  double *out);
