@@ -132,7 +132,9 @@ def test_tile_walk_f32(queue, oracle):
     256 x 128 x 256 against mode 3 (the 4-wave walk's body) and the f64 dd
     oracle. f32 dots keep f32 pairs, which are not split-independent (§6),
     so the bars are tolerances: a wrong neighbour or edge would be far
-    outside them."""
+    outside them. (The f32 loop's arithmetic, mode 6's second walk included,
+    is held bit for bit to the exact-dot model at smaller sizes in
+    tests/test_gpu_f32.py.)"""
     dims = (3, 256, 128, 256)
     rp, cl, vl = oracle.poisson(*dims)
     n = len(rp) - 1

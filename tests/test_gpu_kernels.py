@@ -67,11 +67,13 @@ def test_spmv_long_row(queue, oracle):
 
 
 def test_spmv_f32(queue, oracle):
+    # every row, bit for bit, against the per-row loop in f32 (tests/cg_model.py;
+    # tests/test_gpu_f32.py has the irregular matrices and the forced variants)
+    from tests import cg_model
     rp, cl, vl = oracle.poisson(2, 64, 64, 1)
     x = np.random.default_rng(2).standard_normal(len(rp) - 1).astype(np.float32)
     y = _spmv(queue, rp, cl, vl, x, dtype=np.float32)
-    yr = oracle.spmv(rp, cl, vl, x.astype(np.float64))
-    np.testing.assert_allclose(y, yr, rtol=1e-5, atol=1e-5)
+    np.testing.assert_array_equal(y, cg_model.spmv(rp, cl, vl.astype(np.float32), x))
 
 
 @pytest.mark.parametrize("n", [1, 2, 255, 256, 4097, 1_000_003])
@@ -180,6 +182,8 @@ def test_cg_tol_zero_runs_to_cap_or_nan(oracle):
 
 
 def test_cg_f32(oracle):
+    """A loose end-to-end bar through the Python mirror. The f32 loop's
+    arithmetic is held bit for bit in tests/test_gpu_f32.py."""
     rp, cl, vl = oracle.poisson(2, 32, 32, 1)
     b = np.arange(1, len(rp), dtype=np.float64)
     cg = cga.CG.createCG(dtype=np.float32)
