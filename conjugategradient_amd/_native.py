@@ -118,6 +118,17 @@ _SIGS = {
     "cgx_cg_run_batch": (_i32, [_vp, _i64, C.POINTER(_i64), C.POINTER(_i32)]),
     "cgx_cg_set_batch_form": (_i32, [_vp, _i32]),
     "cgx_cg_batch_info": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "cgx_mixed_create": (_i32, [_vp, _vp, C.POINTER(_vp)]),
+    "cgx_mixed_destroy": (_i32, [_vp]),
+    "cgx_mixed_config": (_i32, [_vp, _dbl, _i32, _i64]),
+    "cgx_mixed_set_mode": (_i32, [_vp, _i32]),
+    "cgx_mixed_set_precond": (_i32, [_vp, _i32, _vp]),
+    "cgx_mixed_solve": (_i32, [_vp, _vp, _vp, _dbl, _i64, C.POINTER(_i32), C.POINTER(_i64),
+                               C.POINTER(_dbl), C.POINTER(_i32)]),
+    "cgx_mixed_history": (_i32, [_vp, C.POINTER(_dbl), C.POINTER(_i64), C.POINTER(_dbl), _i32,
+                                 C.POINTER(_i32)]),
+    "cgx_mixed_inner": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "cgx_mixed_bytes": (_i32, [_vp, C.POINTER(_i64)]),
     "cgx_accuracy": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_dbl)]),
     "cgx_poisson_nnz": (_i64, [_i32, _i32, _i32, _i32, _i64, _i64]),
     "cgx_poisson_fill": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),

@@ -384,6 +384,12 @@ class CG:
         self.iterations_batch = None  # extension (solve_batch): loop bodies per column
         self.final_rxr_batch = None   # r.r after each column's last body
         self.stopped_batch = None     # 1 stop rule / NaN, 2 cap reached, per column
+        self._mixed = None        # cgx_mixed handle (solve_mixed), built on first use
+        self._mixed_for = None
+        self._mixed_cfg = None    # the (mode, preconditioner) its inner solver was given
+        self.outer_steps = 0      # extension (solve_mixed): corrections applied
+        self.mixed_status = None  # 1 tolerance, 2 cap, 3 stagnated, 4 NaN
+        self.mixed_history = None  # [(f64 r.r, inner bodies, inner final f32 r.r)]
 
     @classmethod
     def createCG(cls, dtype=np.float64, debug=Debuglevel.None_, device: int = 0) -> "CG":
@@ -398,6 +404,7 @@ class CG:
         else:
             self.A.init(data, columns, rows)
         self._drop_solver()
+        self._drop_mixed()
 
     def getDimension(self) -> int:
         """:156"""
@@ -504,6 +511,91 @@ class CG:
             self.final_rz = rz.value
         self.is_solved = True
 
+    def _drop_mixed(self):
+        if self._mixed:
+            lib().cgx_mixed_destroy(self._mixed)
+        self._mixed = None
+        self._mixed_for = None
+        self._mixed_cfg = None
+
+    def solve_mixed(self, improvement: float = 0.0, max_iter: int = -1,
+                    inner_reduction: float = 0, max_outer: int = 0, inner_cap: int = 0,
+                    fallback: bool = True) -> None:
+        """Extension (cgx_mixed_solve): the f64 system solved to
+        ``improvement`` on the true f64 residual with the loop bodies run by
+        the f32 solver on a cast copy of the matrix (iterative refinement).
+        f64 ``CG`` only (TypeError otherwise, before any device call).
+        ``mode`` is the inner solver's mode and ``setPreconditioner`` its
+        preconditioner (a caller's diagonal is cast to f32). ``max_iter`` caps
+        the inner bodies of the whole call; ``inner_reduction``, ``max_outer``
+        and ``inner_cap``: 0 keeps the default (1e-5, 8, N + 1), ValueError
+        for a negative or non-finite value. Sets ``iterations`` (inner
+        bodies), ``outer_steps``, ``final_rxr`` (the last true r.r),
+        ``mixed_status`` (1 tolerance reached, 2 cap, 3 stagnated, 4 NaN) and
+        ``mixed_history`` ([(r.r, inner bodies, inner final r.r)] per residual
+        evaluation). With ``fallback`` a status 3 or 4 continues with the
+        ordinary f64 ``solve`` from the current x; its bodies are added to
+        ``iterations`` and ``mixed_status`` keeps the 3 or 4."""
+        if self.dtype != np.float64:
+            raise TypeError(f"solve_mixed refines a float64 system; this CG is {self.dtype}")
+        if not (np.isfinite(inner_reduction) and inner_reduction >= 0):
+            raise ValueError(f"inner_reduction {inner_reduction!r} must be finite and not negative")
+        if int(max_outer) < 0:
+            raise ValueError(f"max_outer {max_outer!r} must not be negative")
+        if int(inner_cap) < 0:
+            raise ValueError(f"inner_cap {inner_cap!r} must not be negative")
+        if self.b.ptr() is None:
+            raise RuntimeError("No right hand side to solve for")
+        if self.A.columns() is None:
+            raise RuntimeError("No Matrix given")
+        n = self.A.N()
+        if self.x.ptr() is None:
+            self.x = Vector(self._queue, n, dtype=self.dtype)
+        L = lib()
+        sched = self.A.schedule()
+        if self._mixed is None or self._mixed_for != sched:
+            self._drop_mixed()
+            h = _vp()
+            check(L.cgx_mixed_create(self._queue.handle, sched, C.byref(h)))
+            self._mixed, self._mixed_for = h, sched
+        m = self._mixed
+        inner = _vp()
+        check(L.cgx_mixed_inner(m, None, C.byref(inner)))
+        check(L.cgx_cg_config(inner, self.poll_every, 1 if self.use_graph else 0))
+        # (mode before the preconditioner, and NONE first: whichever of the two
+        # comes second refuses a mode that runs no preconditioner)
+        cfg = (self.mode, self._precond, self._minv)
+        if cfg != self._mixed_cfg:  # (setting either drops the inner solver's captured graphs)
+            self._mixed_cfg = None
+            check(L.cgx_mixed_set_precond(m, int(Preconditioner.None_), None))
+            check(L.cgx_mixed_set_mode(m, self.mode))
+            if self._precond != Preconditioner.None_:
+                if self._precond == Preconditioner.Diagonal and self._minv.N() != n:
+                    raise ValueError(f"diag has {self._minv.N()} entries, the matrix {n} rows")
+                check(L.cgx_mixed_set_precond(
+                    m, int(self._precond),
+                    self._minv.ptr() if self._precond == Preconditioner.Diagonal else None))
+            self._mixed_cfg = cfg
+        check(L.cgx_mixed_config(m, float(inner_reduction), int(max_outer), int(inner_cap)))
+        outer, bodies, rxr, status = C.c_int(0), C.c_int64(0), C.c_double(0), C.c_int(0)
+        check(L.cgx_mixed_solve(m, self.b.ptr(), self.x.ptr(), float(improvement), int(max_iter),
+                                C.byref(outer), C.byref(bodies), C.byref(rxr), C.byref(status)))
+        cnt = C.c_int(0)
+        check(L.cgx_mixed_history(m, None, None, None, 0, C.byref(cnt)))
+        k = cnt.value
+        rr, ib, ir = (C.c_double * k)(), (C.c_int64 * k)(), (C.c_double * k)()
+        check(L.cgx_mixed_history(m, rr, ib, ir, k, C.byref(cnt)))
+        self.mixed_history = [(rr[i], ib[i], ir[i]) for i in range(k)]
+        self.iterations = bodies.value
+        self.outer_steps = outer.value
+        self.final_rxr = rxr.value
+        self.final_rz = float("nan")
+        self.mixed_status = status.value
+        self.is_solved = True
+        if fallback and status.value in (3, 4):
+            self.solve(improvement, max_iter)
+            self.iterations += bodies.value
+
     MAX_BATCH = 8  # cgx.h: a batch has 1 to 8 right-hand sides
 
     def solve_batch(self, B, X0=None, improvement: float = 0.0, max_iter: int = -1) -> np.ndarray:
@@ -583,6 +675,7 @@ class CG:
 
     def __del__(self):  # pragma: no cover
         try:
+            self._drop_mixed()
             self._drop_solver()
         except Exception:
             pass

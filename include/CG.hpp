@@ -22,10 +22,12 @@
 #include <cstdlib>
 #include <exception>
 #include <iostream>
+#include <limits>
 #include <memory>
 #include <ostream>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -40,6 +42,11 @@ namespace detail {
 struct CgDeleter {
   void operator()(cgx_cg *c) const {
     if (c) cgx_cg_destroy(c);
+  }
+};
+struct MixedDeleter {
+  void operator()(cgx_mixed *m) const {
+    if (m) cgx_mixed_destroy(m);
   }
 };
 }  // namespace detail
@@ -79,12 +86,14 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
     if constexpr (debug == Debuglevel::Verbose) std::clog << "Setting Matrix\n";
     A.init(data, columns, rows);
     _solver.reset();
+    _mixed.reset();
   }
 
   /** :102 — a device matrix, moved */
   void setMatrix(Matrix &&M) {
     A = std::forward<Matrix>(M);
     _solver.reset();
+    _mixed.reset();
   }
 
   /** :156 */
@@ -269,6 +278,99 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
   const std::vector<double> &batchFinalResidualSquared() const { return _batch_rxr; }
   const std::vector<int> &batchStopped() const { return _batch_stopped; }
 
+  /** one residual evaluation of solveMixed (cgx_mixed_history) */
+  struct MixedRecord {
+    double rr;               ///< the f64 true r.r
+    long long inner_bodies;  ///< bodies of the inner solve before it (0 for the first)
+    double inner_rxr;        ///< that solve's final f32 r.r (of the scaled system)
+  };
+  /**
+   * Mixed-precision solve (cgx_mixed_solve of cgx.h; CG<double> only): A x = b
+   * to `improvement` on the true f64 residual, the loop bodies run by the f32
+   * solver on a cast copy of the matrix (iterative refinement). The
+   * preconditioner set here applies inside (a Diagonal vector is cast to
+   * f32), setMixedInnerMode picks the inner solver's mode, setMaxIterations
+   * caps the inner bodies of the whole call. inner_reduction, max_outer and
+   * inner_cap: 0 keeps the default (1e-5, 8, N + 1). Sets iterations() (inner
+   * bodies), outerSteps(), finalResidualSquared() (the last true r.r),
+   * mixedStatus() (1 tolerance reached, 2 cap, 3 stagnated, 4 NaN) and
+   * mixedHistory(). With `fallback` a status 3 or 4 continues with the
+   * ordinary solve() from the current x; its bodies are added to iterations()
+   * and mixedStatus() keeps the 3 or 4.
+   * @throw std::invalid_argument for a negative or non-finite knob
+   * @throw std::runtime_error if b or A is missing
+   */
+  void solveMixed(DT improvement = static_cast<DT>(0), double inner_reduction = 0,
+                  int max_outer = 0, long long inner_cap = 0, bool fallback = true) {
+    static_assert(std::is_same<DT, double>::value, "solveMixed refines a double system");
+    if (!(inner_reduction >= 0) || inner_reduction > std::numeric_limits<double>::max())
+      throw std::invalid_argument("solveMixed: inner_reduction must be finite and not negative");
+    if (max_outer < 0) throw std::invalid_argument("solveMixed: max_outer must not be negative");
+    if (inner_cap < 0) throw std::invalid_argument("solveMixed: inner_cap must not be negative");
+    if (this->b.data() == nullptr) throw std::runtime_error("No right hand side to solve for");
+    if (this->A.columns().get() == nullptr) throw std::runtime_error("No Matrix given");
+    if (x.ptr() == nullptr) x.init_empty(A.N());
+    cgx_csr *sched = A.schedule();
+    if (!_mixed || _mixed_for != sched) {
+      cgx_mixed *m = nullptr;
+      check(cgx_mixed_create(_queue.native(), sched, &m), "cgx_mixed_create");
+      _mixed = std::shared_ptr<cgx_mixed>(m, detail::MixedDeleter());
+      _mixed_for = sched;
+      _mixed_set = false;
+    }
+    cgx_mixed *m = _mixed.get();
+    if (!_mixed_set || _mixed_mode_set != _mixed_mode || _mixed_precond_set != _precond ||
+        _mixed_minv_set != _minv.ptr()) {
+      // mode before the preconditioner, and None first: whichever of the two
+      // comes second refuses a mode that runs no preconditioner
+      _mixed_set = false;
+      check(cgx_mixed_set_precond(m, CGX_PRECOND_NONE, nullptr), "solveMixed");
+      check(cgx_mixed_set_mode(m, _mixed_mode), "setMixedInnerMode");
+      if (_precond != Preconditioner::None) {
+        if (_precond == Preconditioner::Diagonal &&
+            static_cast<std::size_t>(_minv.N()) != static_cast<std::size_t>(A.N()))
+          throw std::invalid_argument("setPreconditioner: the diagonal's length is not N");
+        check(cgx_mixed_set_precond(m, static_cast<int>(_precond),
+                                    _precond == Preconditioner::Diagonal ? _minv.ptr() : nullptr),
+              "setPreconditioner");
+      }
+      _mixed_set = true;
+      _mixed_mode_set = _mixed_mode;
+      _mixed_precond_set = _precond;
+      _mixed_minv_set = _minv.ptr();
+    }
+    check(cgx_mixed_config(m, inner_reduction, max_outer, inner_cap), "solveMixed");
+    int outer = 0, status = 0;
+    int64_t bodies = 0;
+    double rxr = 0;
+    check(cgx_mixed_solve(m, b.ptr(), x.ptr(), (double)improvement, _max_iterations, &outer,
+                          &bodies, &rxr, &status),
+          "solveMixed");
+    int count = 0;
+    check(cgx_mixed_history(m, nullptr, nullptr, nullptr, 0, &count), "solveMixed");
+    std::vector<double> rr(count), irxr(count);
+    std::vector<int64_t> ib(count);
+    check(cgx_mixed_history(m, rr.data(), ib.data(), irxr.data(), count, &count), "solveMixed");
+    _mixed_history.clear();
+    for (int i = 0; i < count; ++i) _mixed_history.push_back({rr[i], (long long)ib[i], irxr[i]});
+    _iterations = bodies;
+    _final_rxr = rxr;
+    _outer_steps = outer;
+    _mixed_status = status;
+    this->is_solved = true;
+    if (fallback && (status == 3 || status == 4)) {
+      solve(improvement);
+      _iterations += bodies;
+    }
+  }
+  /** the inner f32 solver's mode (cgx_cg_set_mode; 0 auto) for the following solveMixed */
+  void setMixedInnerMode(int mode) { _mixed_mode = mode; }
+  int outerSteps() const { return _outer_steps; }
+  int mixedStatus() const { return _mixed_status; }
+  const std::vector<MixedRecord> &mixedHistory() const { return _mixed_history; }
+  /** the cgx_mixed handle of the last solveMixed (null before one): cgx_mixed_inner, cgx_mixed_bytes */
+  cgx_mixed *mixedHandle() const { return _mixed.get(); }
+
  private:
   void executeQueue() {
     try {
@@ -322,6 +424,15 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
   std::vector<long long> _batch_iterations;
   std::vector<double> _batch_rxr;
   std::vector<int> _batch_stopped;
+  std::shared_ptr<cgx_mixed> _mixed;
+  cgx_csr *_mixed_for = nullptr;
+  // what the inner solver was last given (setting either drops its captured graphs)
+  bool _mixed_set = false;
+  int _mixed_mode = 0, _mixed_mode_set = 0;
+  Preconditioner _mixed_precond_set = Preconditioner::None;
+  const void *_mixed_minv_set = nullptr;
+  int _outer_steps = 0, _mixed_status = 0;
+  std::vector<MixedRecord> _mixed_history;
 };
 
 };  // namespace CGSolver

@@ -418,6 +418,76 @@ int cgx_cg_set_batch_form(cgx_cg *cg, int form);
  * in effect). */
 int cgx_cg_batch_info(cgx_cg *cg, int *form_in_effect, int *width);
 
+/* ---- cgx_mixed: an f64 system solved with f32 bodies (replaces nothing in
+ * the reference, whose solve runs in one precision) -----------
+ * Iterative refinement: A x = b in f64 is solved to `tol` on the TRUE f64
+ * residual, the loop bodies run by the f32 solver (cgx_cg, any mode, format,
+ * graph replay, preconditioner) on A32, A's values cast once to f32. Per outer
+ * step the f64 work is one SpMV (cgx_spmv's launch on A) and three streaming
+ * kernels. The loop, with tot = 0 and prev = +inf:
+ *   r = b - A x; rr = r.r (double-length sum, rounded once); nr = sqrt(rr)
+ *   record (rr, bodies and final f32 r.r of the previous inner solve; 0, 0 first)
+ *   rr NaN or Inf -> status 4; nr <= tol -> 1; nr > 0.5 prev -> 3 (stagnated:
+ *   less than one bit gained); o == max_outer or tot >= cap -> 2
+ *   prev = nr; nr = f 2^e, f in [0.5, 1); s = 2^-e
+ *   r32 = (float)(r s) (one rounding to nearest even, subnormals kept), d32 = 0
+ *   f32 CG on A32 d = r32, absolute tolerance max(inner_reduction, 0.5 tol s),
+ *   at most min(n + 1, inner_cap, cap - tot) bodies
+ *   its final r.r NaN -> status 4, the correction NOT applied (this includes an
+ *   inner system solved exactly, n = 1 or a diagonal A: stop rule Q5 runs one
+ *   more body on r.r = 0), its bodies not counted
+ *   x += (double)d32 2^e (product exact, one add); tot += its bodies
+ * tol is absolute on sqrt(r.r) and cap is max_bodies, both as cgx_cg_solve's
+ * (max_bodies < 0: n + 1); cap counts inner bodies over the whole call. */
+typedef struct cgx_mixed cgx_mixed;
+/* A: f64, single device (an f32 matrix: CGX_EINVAL, a partitioned one:
+ * CGX_EUNSUPPORTED), values 16-byte aligned, alive (with its arrays) until
+ * cgx_mixed_destroy. Builds the f32 values (A's rowptr and col are shared, not
+ * rewritten), an f32 cgx_csr through cgx_csr_create (autotune included), an
+ * f32 cgx_cg and the vectors r, Ax, r32, d32. CGX_EINVAL when a value of A
+ * casts to +-inf or a non-zero value casts to 0 (the message gives the count
+ * and the first entry). Blocking. Replaces nothing in the reference. */
+int cgx_mixed_create(cgx_ctx *ctx, cgx_csr *A, cgx_mixed **out);
+/* Replaces nothing in the reference. */
+int cgx_mixed_destroy(cgx_mixed *m);
+/* inner_reduction (default 1e-5: about what f32 CG delivers before its
+ * recursive residual leaves the true one), max_outer (8), inner_cap (n + 1);
+ * 0 keeps a default, CGX_EINVAL for a negative or non-finite value.
+ * Replaces nothing in the reference. */
+int cgx_mixed_config(cgx_mixed *m, double inner_reduction, int max_outer, int64_t inner_cap);
+/* cgx_cg_set_mode on the inner solver. Replaces nothing in the reference. */
+int cgx_mixed_set_mode(cgx_mixed *m, int mode);
+/* cgx_cg_set_precond on the inner solver. JACOBI: 1 / a_ii formed in f32 from
+ * A32. DIAGONAL: d_minv = n f64 device values (16-byte aligned), of which an
+ * f32 copy is made and owned here (the caller's need not outlive the call);
+ * CGX_EINVAL when a value is not positive and finite after the cast (the
+ * message names the first entry). A mode that refuses a preconditioner fails
+ * as cgx_cg_set_precond does. Blocking. Replaces nothing in the reference. */
+int cgx_mixed_set_precond(cgx_mixed *m, int kind, const void *d_minv);
+/* Blocking. d_b, d_x: n f64 device values, 16-byte aligned; d_x holds the
+ * initial guess and receives the result. Outputs (each may be NULL): *outer
+ * corrections applied, *inner_bodies f32 bodies counted against the cap, *rxr
+ * the last f64 true r.r (the one that decided the status), *status 1 tol
+ * reached, 2 max_outer or the body cap, 3 stagnated, 4 NaN (x is the last
+ * finite iterate). The outer steps launch eagerly; the inner solves replay
+ * their graphs. Replaces nothing in the reference. */
+int cgx_mixed_solve(cgx_mixed *m, const void *d_b, void *d_x, double tol, int64_t max_bodies,
+                    int *outer, int64_t *inner_bodies, double *rxr, int *status);
+/* One record per residual evaluation of the last solve: rr[i] the f64 r.r,
+ * inner_bodies[i] / inner_rxr[i] the bodies and final f32 r.r (of the scaled
+ * system) of the inner solve before it (0 / 0 for the first). *count = the
+ * records; up to `cap` are written. Replaces nothing in the reference. */
+int cgx_mixed_history(cgx_mixed *m, double *rr, int64_t *inner_bodies, double *inner_rxr, int cap,
+                      int *count);
+/* Borrowed handles of the f32 matrix and the inner solver: the info, timing
+ * and configuration calls work on them; do not destroy them.
+ * Replaces nothing in the reference. */
+int cgx_mixed_inner(cgx_mixed *m, cgx_csr **A32, cgx_cg **cg32);
+/* Device bytes the object holds on top of A: the f32 values, its vectors, the
+ * f32 matrix's schedule and formats and the inner solver's buffers, each at
+ * its allocated size, as of the call. Replaces nothing in the reference. */
+int cgx_mixed_bytes(cgx_mixed *m, int64_t *bytes);
+
 /* CG::accuracy (CG.hpp:463-515): blocking; |sum (b-Ax)^2 / sum x^2|. */
 int cgx_accuracy(cgx_ctx *ctx, cgx_csr *A, const void *d_b, const void *d_x,
                  double *out);
