@@ -171,7 +171,8 @@ int harvest_events(cgx_cg *cg, int64_t active_iters) {
         cg->t_exec_calls[kid] += 1;
       }
     }
-    if (kid == last_kid) ++iter_seen;
+    // (mode 7's slot 3 ends its body with the fused kernel 3 instead of kernel 2)
+    if (kid == last_kid || (kid == 3 && cg->fdefer && cg->recompute)) ++iter_seen;
   }
   cg->ev_pending.clear();
   cg->ev_used = 0;
@@ -520,20 +521,22 @@ template <typename T> int enqueue_iter_fdefer(cgx_cg *cg, int slot) {
   if (cg->recompute) {
     // mode 7: kernel 1 forms p_k into P[slot] with p.Ap only (the tile walk,
     // no Ap vector), kernel 2 forms A p_k again from it and updates r with
-    // the stop rule; slot 3 applies the group's x updates after it
-    // (k_flush_group). 60 N bytes per body against mode 6's 66 N.
+    // the stop rule; in slot 3 its epilogue also applies the group's x
+    // updates (k_spmv_lean_updr_rule_flush, timed as kernel 3 so kernel 2's
+    // average stays the plain walk's). 58 N bytes per body against mode 6's
+    // 66 N.
     if ((rc = timed(cg, 1, s, [&] {
            return Launch<T>::fd_dot_tile(A->dev, r, P[(slot + 3) & 3], P[slot], st, slot, ws,
                                          A->dev.vl_grid, s, par);
          })))
       return rc;
-    if ((rc = timed(cg, 2, s, [&] {
-           return Launch<T>::lean_updr_rule(A->dev, P[slot], r, st, slot, ws, s, rpar);
-         })))
-      return rc;
     if (slot == 3)
-      return timed(cg, 3, s, [&] { return Launch<T>::flush_group(cg->n, x, P, st, s, par); });
-    return CGX_OK;
+      return timed(cg, 3, s, [&] {
+        return Launch<T>::lean_updr_rule_flush(A->dev, r, st, ws, s, rpar, x, P);
+      });
+    return timed(cg, 2, s, [&] {
+      return Launch<T>::lean_updr_rule(A->dev, P[slot], r, st, slot, ws, s, rpar);
+    });
   }
   const int npp = Launch<T>::fd_parts(A->dev);
   if ((rc = timed(cg, 1, s, [&] {
@@ -3240,7 +3243,7 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
     if (mode == 3 && !cg->A->dist && vl_whole(cg->A->dev)) {
       mode = 6;
       // where mode 7's first kernel runs the ring walk (f64): p_k formed in
-      // that walk, 60 N bytes per body against 66 N — 5,643-5,754 against
+      // that walk, then 60 N bytes per body against 66 N — 5,643-5,754 against
       // 5,286-5,315 it/s in mode 6 at 256^3, 6 interleaved runs each
       // (profiles/ring_ab.log; 256 x 128 x 256: 9,879 against 8,702). With
       // the per-wave tile walk mode 7 stays behind mode 6 (4,827 it/s)

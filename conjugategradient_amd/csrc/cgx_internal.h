@@ -320,8 +320,6 @@ template <typename T> struct Launch {
   static hipError_t spmv_fd(const CsrDev &A, const T *r, const T *pold, T *pc, T *Ap,
                             CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr,
                             hipStream_t s, int rev = 0);
-  static hipError_t flush_group(int64_t n, T *x, T *const P[4], CgScalars<T> *st,
-                                hipStream_t s, int rev = 0);
   // a partitioned matrix's boundary rows: CSR-stream over the row blocks
   // `blocks` (count), partials at [part_off, part_off + grid); with P the
   // ghosts come from the peer landing buffer after the neighbours' pushes
@@ -341,6 +339,9 @@ template <typename T> struct Launch {
                                 hipStream_t s, int rev);
   static hipError_t lean_updr_rule(const CsrDev &A, const T *p, T *r, CgScalars<T> *st, int slot,
                                    RedWs<T> *ws, hipStream_t s, int rev);
+  // slot 3's: p = P[3], and the group's x updates in the walk's epilogue
+  static hipError_t lean_updr_rule_flush(const CsrDev &A, T *r, CgScalars<T> *st, RedWs<T> *ws,
+                                         hipStream_t s, int rev, T *x, T *const P[4]);
   static hipError_t lean_updr(const CsrDev &A, const T *p, T *r, CgScalars<T> *st, int slot,
                               RedWs<T> *ws, hipStream_t s, int rev);
   // a partitioned matrix's interior slices by the lean walk (A.vl_split), the

@@ -2608,6 +2608,79 @@ template <typename T> struct EpiUpdR {
     if (l1) acc += v1 * v1;
   }
 };
+// Mode 7, kernel 2 of slot 3: EpiUpdR with the group's deferred x updates
+// riding the same rows (the walk visits every row once), x = (((x + a0 p0) +
+// a1 p1) + a2 p2) + a3 p3 over the slots whose use flag is set:
+// flush_group_range's expression in its order, so its values bit for bit.
+// x and p0 .. p2 are loaded with r, before the sums; p3 is this launch's p_k,
+// the center pair a lean slice hands to pre2c (a generic slice loads it).
+// Non-temporal as the group flush of vectors above kNtVecBytes (mode 7's
+// sizes): x and the old p buffers are not read again before the next group.
+template <typename T> struct EpiUpdRFlush {
+  using PU = typename PairU<T>::V;
+  EpiUpdR<T> u;  // r and r.r
+  T *__restrict__ x;
+  const T *__restrict__ P0, *__restrict__ P1, *__restrict__ P2, *__restrict__ P3;
+  T a0, a1, a2;  // (a3: u.alpha)
+  bool use0, use1, use2;
+  PU xv, q0, q1, q2, q3;
+  __device__ __forceinline__ void load_pair(int i) {
+    xv = __builtin_nontemporal_load(reinterpret_cast<const PU *>(x + i));
+    q0 = __builtin_nontemporal_load(reinterpret_cast<const PU *>(P0 + i));
+    q1 = __builtin_nontemporal_load(reinterpret_cast<const PU *>(P1 + i));
+    q2 = __builtin_nontemporal_load(reinterpret_cast<const PU *>(P2 + i));
+  }
+  __device__ __forceinline__ void pre(int i) {
+    u.pre(i);
+    xv.x = x[i];
+    q0.x = P0[i];
+    q1.x = P1[i];
+    q2.x = P2[i];
+    q3.x = P3[i];
+  }
+  __device__ __forceinline__ void pre2c(int i0, int i1, T c0, T c1) {
+    u.pre2(i0, i1);
+    load_pair(i0);  // (i1 == i0 + 1)
+    q3.x = c0;
+    q3.y = c1;
+  }
+  __device__ __forceinline__ void pre2(int i0, int i1) {
+    u.pre2(i0, i1);
+    if (i1 == i0 + 1) {
+      load_pair(i0);
+      q3 = *reinterpret_cast<const PU *>(P3 + i0);
+    } else {
+      pre(i0);
+      xv.y = x[i1];
+      q0.y = P0[i1];
+      q1.y = P1[i1];
+      q2.y = P2[i1];
+      q3.y = P3[i1];
+    }
+  }
+  __device__ __forceinline__ T upd(T v, T b0, T b1, T b2, T b3) const {
+    if (use0) v = v + a0 * b0;
+    if (use1) v = v + a1 * b1;
+    if (use2) v = v + a2 * b2;
+    return v + u.alpha * b3;
+  }
+  __device__ __forceinline__ void row(int i, T s) {
+    u.row(i, s);
+    x[i] = upd(xv.x, q0.x, q1.x, q2.x, q3.x);
+  }
+  __device__ __forceinline__ void row2(int i, T s0, T s1, bool l0, bool l1) {
+    u.row2(i, s0, s1, l0, l1);
+    PU v;
+    v.x = upd(xv.x, q0.x, q1.x, q2.x, q3.x);
+    v.y = upd(xv.y, q0.y, q1.y, q2.y, q3.y);
+    if (l0 && l1) {
+      __builtin_nontemporal_store(v, reinterpret_cast<PU *>(x + i));
+    } else {
+      if (l0) x[i] = v.x;
+      if (l1) x[i + 1] = v.y;
+    }
+  }
+};
 template <typename T> struct EpiAccuracy {  // CG.hpp:489-497
   const T *__restrict__ b;
   const T *__restrict__ x;
@@ -3427,7 +3500,7 @@ __global__ __launch_bounds__(kBlock, kTileW) void k_spmv_lean_dot_tile(CsrArgs A
   store_part(ws->pap_part, blockIdx.x, e.acc, sm.red);
 }
 
-// Mode 7 (cgx_abi.cpp enqueue_iter_fdefer), kernel 1 of 2 (3 in slot 3):
+// Mode 7 (cgx_abi.cpp enqueue_iter_fdefer), kernel 1 of 2:
 // k_spmv_fd_lean's preamble (beta from body k-1's r.r partials, the records,
 // slot 0 opening a group) and its p_k = r + beta p_{k-1} into P[s], in the
 // tile walk: the ring's center pairs are formed once, a step before their
@@ -4496,7 +4569,7 @@ __global__ __launch_bounds__(kBlock) void k_update_r(int64_t n, const T *rin, T 
                                                      rule, nullptr);
 }
 // Mode 4, slot 3: update_r with the stop rule and the group's x flush in one
-// launch (k_flush_group's values, bit for bit)
+// launch (a separate flush launch's values, bit for bit)
 template <typename T, int KP = kPartsPerThread>
 __global__ __launch_bounds__(kBlock) void k_update_r_flush(int64_t n, T *r,
                                                            const T *__restrict__ Ap,
@@ -5460,24 +5533,69 @@ __global__ __launch_bounds__(kBlock) void k_flush_defer(int64_t n, T *__restrict
   flush_group_range<T>(n, x, P0, P1, P2, P3, a, use, 0);
 }
 
+// Mode 7, kernel 2 of slot 3: k_spmv_lean_updr_rule with the group's x flush
+// in the walk's epilogue (EpiUpdRFlush; p = P3, the slot's p_k), as mode 4's
+// k_update_r_flush: the flags and alphas of slots 0 .. 2 were written by
+// earlier launches and are read before the walk, slot 3's are this launch's
+// own (thread 0 of workgroup 0 writes them to st here: never read back).
+// When the body is inactive the group's earlier bodies that ran are applied
+// by flush_group_range over this grid (A.rev: the launch's sweep direction).
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_flush_group(int64_t n, T *__restrict__ x,
-                                                        const T *__restrict__ P0,
-                                                        const T *__restrict__ P1,
-                                                        const T *__restrict__ P2,
-                                                        const T *__restrict__ P3,
-                                                        const CgScalars<T> *st, int rev) {
-  T a[4];
-  bool use[4];
-  bool any = false;
+__global__ __launch_bounds__(kBlock) void k_spmv_lean_updr_rule_flush(
+    CsrArgs A, const T *__restrict__ p, T *__restrict__ r, CgScalars<T> *st, RedWs<T> *ws,
+    int np_pap, T *__restrict__ x, const T *__restrict__ P0, const T *__restrict__ P1,
+    const T *__restrict__ P2) {
+  constexpr int slot = 3;
+  T ga[4] = {T(0), T(0), T(0), T(0)};
+  bool guse[4] = {false, false, false, false};
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    a[t] = st->alpha[t];
-    use[t] = st->ran[t] != 0 && st->skip[t] == 0;
-    any = any || use[t];
+  for (int t = 0; t < 3; ++t) {
+    ga[t] = st->alpha[t];
+    guse[t] = st->ran[t] != 0 && st->skip[t] == 0;
   }
-  if (!any) return;
-  flush_group_range<T>(n, x, P0, P1, P2, P3, a, use, rev);
+  if (!st->active[slot]) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->active[(slot + 1) & 3] = 0;
+    if (guse[0] || guse[1] || guse[2]) flush_group_range<T>(A.n, x, P0, P1, P2, p, ga, guse, A.rev);
+    return;
+  }
+  __shared__ SellLds<T> sm;
+  const T pAp = sum_parts(ws->pap_part, np_pap, sm.red);
+  const T rxr = st->rxr[slot];
+  const T alpha = rxr / pAp;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    st->pAp[slot] = pAp;
+    st->alpha[slot] = alpha;
+    st->skip[slot] = 0;
+    const long long m = st->bodies + 1;  // stop rule, as k_update_xp
+    st->bodies = m;
+    const bool cond = isnan(rxr) || sqrt(rxr) <= st->tol;
+    const bool cont = !cond && m < st->cap;
+    st->active[(slot + 1) & 3] = cont ? 1 : 0;
+    st->stopped = cond ? 1 : (cont ? 0 : 2);
+    st->ran[slot] = 1;
+  }
+  const T *vd = static_cast<const T *>(A.svdict);
+  const unsigned long long *vt = A.vct;
+  if (A.vl_lds) {
+    lean_lds(A, sm);
+    vd = sm.vdict;
+    vt = sm.vt;
+  }
+  EpiUpdRFlush<T> e;
+  e.u = EpiUpdR<T>{r, alpha, T(0), T(0), T(0)};
+  e.x = x;
+  e.P0 = P0;
+  e.P1 = P1;
+  e.P2 = P2;
+  e.P3 = p;
+  e.a0 = ga[0];
+  e.a1 = ga[1];
+  e.a2 = ga[2];
+  e.use0 = guse[0];
+  e.use1 = guse[1];
+  e.use2 = guse[2];
+  spmv_lean<T>(A, GatherX<T>{p}, e, vd, vt);
+  store_part(ws->rr_part, blockIdx.x, e.u.acc, sm.red);
 }
 
 // ---------------------------------------------------------------------------
@@ -6813,10 +6931,15 @@ hipError_t Launch<T>::spmv_dot_slices_push(const CsrDev &A, const int *list, int
 }
 
 template <typename T>
-hipError_t Launch<T>::flush_group(int64_t n, T *x, T *const P[4], CgScalars<T> *st,
-                                  hipStream_t s, int rev) {
-  CGX_LAUNCH(k_flush_group<T>, grid_elems(n, kGridUpdateP), n, x, (const T *)P[0],
-             (const T *)P[1], (const T *)P[2], (const T *)P[3], (const CgScalars<T> *)st, rev);
+hipError_t Launch<T>::lean_updr_rule_flush(const CsrDev &A, T *r, CgScalars<T> *st, RedWs<T> *ws,
+                                           hipStream_t s, int rev, T *x, T *const P[4]) {
+  if (!lean_tile_ok(A)) return hipErrorInvalidValue;
+  CsrArgs a = args(A);
+  a.rev = rev;
+  CGX_GGL(k_spmv_lean_updr_rule_flush<T>, dim3(A.vl_grid), dim3(kBlock), 0, s, a,
+          (const T *)P[3], r, st, ws, fd_dot_parts(A), x, (const T *)P[0], (const T *)P[1],
+          (const T *)P[2]);
+  return hipGetLastError();
 }
 template <typename T>
 hipError_t Launch<T>::update_r_flush(int64_t n, T *r, const T *Ap, CgScalars<T> *st, int slot,

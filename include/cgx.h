@@ -280,7 +280,8 @@ int cgx_cg_config(cgx_cg *cg, int poll_every, int use_graph);
  * Mode 7 (single device, f64, a 3-D stencil whose lean layout takes the tile
  * walk): mode 4's body with no Ap vector — kernel 1 forms p_k into the p ring
  * and keeps p.Ap, kernel 2 walks A p_k again, updates r and runs the stop
- * rule, slot 3 adds the x flush launch (60 N + 2 x matrix bytes per body).
+ * rule; in slot 3 it also applies the group's x updates from the four p
+ * buffers, row by row in the same walk (58 N + 2 x matrix bytes per body).
  * Auto takes 7 instead of 6 where kernel 1 runs the ring form of the tile
  * walk (cgx_csr_lean_ring; 256^3: DESIGN.md §5) and 6 for the other
  * whole-matrix lean walks between mode 4's two bounds.
