@@ -199,7 +199,7 @@ int enqueue_spmv_dot(cgx_cg *cg, T *p, int slot, int rev, int *np) {
     // A split SELL matrix carries the push in the interior launch's first
     // workgroups (k_spmv_dot_push: the xGMI stores overlap the interior
     // slices, one launch less)
-    const bool split = A->split_ni > 0 && (launch_variant(A->dev, A->dtype) & (2048 | 8192));
+    const bool split = A->split_ni > 0 && sell_variant(launch_variant(A->dev, A->dtype));
     const int wg0 = A->peer.dev.nsend * kPushWG;
     // the interior slices by the lean walk (its layout skips the boundary ones)
     const bool lean_in = split && vl_active(A->dev) && A->dev.vl_split;
@@ -255,7 +255,7 @@ int enqueue_spmv_dot(cgx_cg *cg, T *p, int slot, int rev, int *np) {
                               : Launch<T>::slice_grid(A->dev, A->split_nb));
     return CGX_OK;
   }
-  if (halo && A->split_ni > 0 && (launch_variant(A->dev, A->dtype) & (2048 | 8192))) {
+  if (halo && A->split_ni > 0 && sell_variant(launch_variant(A->dev, A->dtype))) {
     bool async = false;
     if ((rc = dist_halo_post(A, p, s, &async))) return rc;
     const bool lean_in = vl_active(A->dev) && A->dev.vl_split;
@@ -464,7 +464,7 @@ template <typename T> int enqueue_iter_defer(cgx_cg *cg, int slot) {
 bool dist_fd_ok(const cgx_csr *A, int dtype) {
   return A->dist && A->peer.on && dtype == CGX_F64 &&
          A->halo.n_ghost + A->halo.send_total > 0 && A->split_ni > 0 &&
-         (launch_variant(A->dev, A->dtype) & (2048 | 8192)) && vl_active(A->dev) &&
+         sell_variant(launch_variant(A->dev, A->dtype)) && vl_active(A->dev) &&
          A->dev.vl_split && A->bnd_nblk > 0;
 }
 
@@ -1583,7 +1583,7 @@ static int sellp_plan_device(cgx_ctx *ctx, int64_t n, int64_t nnz, const int *d_
   return CGX_OK;
 }
 
-// Plane-march plan (variant bit 2097152, cgx_kernels.hip spmv_sellpv_march):
+// Plane-march plan (variant bit kMarch, cgx_kernels.hip spmv_sellpv_march):
 // the most common slice pattern must be {-D, -a, -1, 0, 1, a, D} (3-D
 // 7-point) or {-D, -1, 0, 1, D} (2-D 5-point) with D a positive multiple of
 // the 128-row slice and 1 < a < D. Slices with another pattern (or the same
@@ -2209,7 +2209,6 @@ int lean_mark_split(cgx_csr *A, const std::vector<int> &boundary) {
 
 // the variant under the lean walk: its generic slices' form (4-bit value
 // codes on templates, the pipelined stencil walk's requirements)
-constexpr int kVlBase = 2050 | 32768 | 262144 | 524288 | 1048576 | kVT;
 
 int build_value_codes(cgx_csr *A) {
   if (!A->dev.sl || !A->dev.sell_kind || A->dev.nsl < 1 || A->dev.nnz < 1) return CGX_OK;
@@ -2376,12 +2375,12 @@ extern "C" int cgx_csr_set_sell(cgx_csr *A, int rows_per_lane) {
   DeviceGuard g(A->ctx->device);
   if (rows_per_lane == 0) {
     free_sell(A);
-    if (A->dev.variant & (2048 | 8192)) A->dev.variant = 0;
+    if (sell_variant(A->dev.variant)) A->dev.variant = 0;
     return CGX_OK;
   }
   int rc = build_sell(A, nullptr, nullptr, rows_per_lane);
   if (rc) return rc;
-  if (!A->dev.sl && (A->dev.variant & (2048 | 8192))) A->dev.variant = 0;
+  if (!A->dev.sl && sell_variant(A->dev.variant)) A->dev.variant = 0;
   return CGX_OK;
 }
 
@@ -2397,13 +2396,13 @@ extern "C" int cgx_csr_stream_bytes(cgx_csr *A, int64_t *bytes) {
     *bytes = 4 * (int64_t)A->dev.vl_grid * A->dev.vl_nst + gen * (int64_t)sizeof(SellSlice) +
              8 * (A->vc_chunks - 64 * A->vt_slices) + 512 * (int64_t)A->dev.nvt +
              (int64_t)A->vl_ncls * (int64_t)sizeof(VlClass);
-  } else if ((v & 32768) && (v & kVT))  // template slices read their chunk from LDS
+  } else if ((v & kVc) && (v & kVT))  // template slices read their chunk from LDS
     *bytes = 8 * (A->vc_chunks - 64 * A->vt_slices) + desc + 512 * (int64_t)A->dev.nvt;
-  else if (v & 32768)
-    *bytes = ((v & 262144) ? 8 : 16) * A->vc_chunks + desc;
-  else if (v & 8192)
-    *bytes = es * A->sell_padded + nsl * 2 * kSellRows * ((v & 16384) ? 4 : 1) + desc;
-  else if (v & 2048)
+  else if (v & kVc)
+    *bytes = ((v & kVc4) ? 8 : 16) * A->vc_chunks + desc;
+  else if (v & kSellP)
+    *bytes = es * A->sell_padded + nsl * 2 * kSellRows * ((v & kMask32) ? 4 : 1) + desc;
+  else if (v & kSell)
     *bytes = es * A->sell_padded + 8 * A->sell_idx_words + desc;
   else if (v & kIL)  // the interleaved copy's pairs (a block's first pair may be shared)
     *bytes = (2 * es + 8) * ((A->dev.nnz + 1) / 2) + 4 * (A->dev.n + 1);
@@ -2503,25 +2502,19 @@ extern "C" int cgx_csr_sell_info(cgx_csr *A, int *has_sell, int64_t *padded) {
 }
 
 // A request names a form k_spmv_dot is instantiated for (CGX_SPMV_LIST,
-// the forms cgx_csr_variant reports) or one of the request forms below,
-// which resolve to such a form on a matrix with the right copies (the
-// checks in cgx_csr_set_variant); the lean walk is handled before this.
+// the forms cgx_csr_variant reports) or is a SELL request: kSell or kSellP
+// with bits of kSellBits only (e.g. kSell | kVc | kVc4, 296960), which
+// resolves to a listed form on a matrix with the right copies (the checks
+// in cgx_csr_set_variant); the lean walk is handled before this.
 static bool known_variant(int v) {
-  static const int ok[] = {0,  1,  2,  3,  4,  5,  6,  7,  12, 13, 14, 15, 133, 135, 264, 265, 266,
-                           267, 2048, 2050, 2056, 2058, 6144, 6146, 8192, 8194, 24576, 24578,
-                           34816, 34818, 40960, 40962, 296960, 296962, 559104, 559106,
-                           821248, 821250, 1607680, 1607682, 1869824, 1869826,
-                           9209856, 9209858, 10258434, 12355584, 12355586, 10258432};
-  for (int k : ok)
-    if (k == v) return true;
-  return spmv_listed(v);
+  return spmv_listed(v) || (sell_variant(v) && (v & ~kSellBits) == 0);
 }
 
 extern "C" int cgx_csr_set_variant(cgx_csr *A, int variant) {
   CGX_REQUIRE(A, CGX_EINVAL, "A is NULL");
   if (variant & kVL) {  // the lean stencil walk (at its first grid candidate unless built)
     CGX_REQUIRE((variant & ~kVL) == 0 || (variant & ~kVL) == kVlBase ||
-                    (variant & ~kVL) == ((kVlBase & ~2048) | 8192),
+                    (variant & ~kVL) == ((kVlBase & ~kSell) | kSellP),
                 CGX_EINVAL, "unknown SpMV variant %d (the lean walk is %d)", variant,
                 kVL | kVlBase);
     CGX_REQUIRE(A->dev.sl_t, CGX_EUNSUPPORTED,
@@ -2545,16 +2538,12 @@ extern "C" int cgx_csr_set_variant(cgx_csr *A, int variant) {
   A->dev.lean = false;
   // (a SELL-family request resolves against the matrix's layout, as the
   // autotune's own candidates do; the check below refuses one with no kernel)
-  constexpr int kSellBits = 2 | 16 | 2048 | 4096 | 8192 | 16384 | 32768 | 262144 | 524288 |
-                            1048576 | 2097152 | kVT;
-  CGX_REQUIRE(known_variant(variant) ||
-                  ((variant & (2048 | 8192)) && (variant & ~kSellBits) == 0),
-              CGX_EINVAL, "unknown SpMV variant %d", variant);
-  CGX_REQUIRE(!(variant & (2048 | 8192)) || A->dev.sl, CGX_EUNSUPPORTED,
+  CGX_REQUIRE(known_variant(variant), CGX_EINVAL, "unknown SpMV variant %d", variant);
+  CGX_REQUIRE(!sell_variant(variant) || A->dev.sl, CGX_EUNSUPPORTED,
               "variant %d needs the SELL-64 copy, which this matrix does not have", variant);
-  CGX_REQUIRE(!(variant & 32768) || A->dev.svc, CGX_EUNSUPPORTED,
+  CGX_REQUIRE(!(variant & kVc) || A->dev.svc, CGX_EUNSUPPORTED,
               "variant %d needs SELL-P value codes, which this matrix does not have", variant);
-  CGX_REQUIRE(!(variant & 262144) || A->dev.svc4, CGX_EUNSUPPORTED,
+  CGX_REQUIRE(!(variant & kVc4) || A->dev.svc4, CGX_EUNSUPPORTED,
               "variant %d needs 4-bit value codes (at most 15 distinct values)", variant);
   CGX_REQUIRE(!(variant & kVT) || A->dev.sl_t, CGX_EUNSUPPORTED,
               "variant %d needs value-code templates, which this matrix does not have", variant);
@@ -2563,7 +2552,7 @@ extern "C" int cgx_csr_set_variant(cgx_csr *A, int variant) {
     CGX_REQUIRE(build_il(A), CGX_EUNSUPPORTED,
                 "variant %d: the interleaved val / col copy could not be built", variant);
   }
-  if ((variant & kC16) && !(variant & 8192)) {
+  if ((variant & kC16) && !(variant & kSellP)) {
     DeviceGuard g(A->ctx->device);
     CGX_REQUIRE(build_col16(A), CGX_EUNSUPPORTED,
                 "variant %d needs 16-bit column deltas: a column of this matrix lies more than "
@@ -2653,14 +2642,14 @@ int autotune_spmv(cgx_csr *A) {
         return CGX_EINVAL;
       }
     }
-    if (!(v & (2048 | 8192 | kVL))) free_sell(A);
+    if (!sell_variant(v) && !(v & kVL)) free_sell(A);
     return CGX_OK;
   }
   const int64_t bytes = A->dev.nnz * (int64_t)(dtype_size(A->dtype) + sizeof(int));
   if (bytes < (int64_t(64) << 20)) {  // small: the size heuristic, SELL where built
     if (A->dev.sl)
-      A->dev.variant = (A->dev.svc4 ? (2048 | 32768 | 262144) : A->dev.svc ? (2048 | 32768) : 2048) |
-                       (A->dev.svc && A->dev.sell_maxw <= 8 ? 524288 | 1048576 : 0);
+      A->dev.variant = (A->dev.svc4 ? kSell | kVc | kVc4 : A->dev.svc ? kSell | kVc : kSell) |
+                       (A->dev.svc && A->dev.sell_maxw <= 8 ? kVcPipe | kVcSt : 0);
     return CGX_OK;
   }
   // (the software-pipelined SELL forms, 2056/2058, measured slower than the
@@ -2674,32 +2663,34 @@ int autotune_spmv(cgx_csr *A) {
   // cache-resident CSR also tries the unpipelined paired loop (5) and the
   // quad loads (265): the G3 stand-in's SpMV runs 23.6 / 23.8 us in them
   // against 25.3 in the pipelined 13 (profiles/r02_irr_variants.log)
-  std::vector<int> cands = big ? std::vector<int>{15} : std::vector<int>{13, 15, 5, 265};
+  std::vector<int> cands =
+      big ? std::vector<int>{kCsrPipe | kNt}
+          : std::vector<int>{kCsrPipe, kCsrPipe | kNt, kCsrPair, kCsrQuad | kXcd};
   // and the paired loop on 16-bit column deltas (10 B per entry) where they fit
-  if (!big && build_col16(A)) cands.push_back(133);
+  if (!big && build_col16(A)) cands.push_back(kCsrPair | kC16);
   // (the pipelined paired loop on the interleaved val / col copy, kIL, is
   // not a candidate: 376 against 373 us at 256^3, 25.3 against 24.9 on the
   // G3 stand-in, 306 against 297 at 4096^2, its stream-only ablation 336
   // against 324 — profiles/r6f_tune_il_*.log; reachable by request)
   if (A->dev.sl) {
-    if (!big) cands.push_back(2048);
-    cands.push_back(2050);
+    if (!big) cands.push_back(kSell);
+    cands.push_back(kSell | kNt);
   }
   // SELL-P value codes: 1 B per slot instead of 8 (4-bit codes: 0.5 B), and
-  // their software-pipelined loop (bit 524288) where no slice is over 8 wide,
+  // their software-pipelined loop (bit kVcPipe) where no slice is over 8 wide,
   // that loop with the +-1 neighbours taken from the adjacent lanes (bit
-  // 1048576: one gather pair fewer per offset -1 / +1)
-  for (int c4 : {0, 262144}) {
+  // kVcSt: one gather pair fewer per offset -1 / +1)
+  for (int c4 : {0, kVc4}) {
     if (!A->dev.svc || (c4 && !A->dev.svc4)) continue;
     // (a y-march form measured 93-124 us against 72 for the templated
     // consecutive walk at 256^3, profiles/r03_ymarch_tune.log: removed)
-    for (int pipe : {0, 524288, 524288 | 1048576, 524288 | 1048576 | 2097152,
-                     524288 | kVT, 524288 | 1048576 | kVT, 524288 | 1048576 | 2097152 | kVT}) {
+    for (int pipe : {0, kVcPipe, kVcPipe | kVcSt, kVcPipe | kVcSt | kMarch, kVcPipe | kVT,
+                     kVcPipe | kVcSt | kVT, kVcPipe | kVcSt | kMarch | kVT}) {
       if (pipe && A->dev.sell_maxw > 8) continue;
-      if ((pipe & 2097152) && A->dev.march_k < 1) continue;
+      if ((pipe & kMarch) && A->dev.march_k < 1) continue;
       if ((pipe & kVT) && (!c4 || !A->dev.sl_t)) continue;
-      if (!big) cands.push_back(2048 | 32768 | c4 | pipe);
-      cands.push_back(2050 | 32768 | c4 | pipe);
+      if (!big) cands.push_back(kSell | kVc | c4 | pipe);
+      cands.push_back(kSell | kNt | kVc | c4 | pipe);
     }
   }
   // preference order: the most specialised form first (the list above grows
@@ -2740,7 +2731,7 @@ int autotune_spmv(cgx_csr *A) {
         return split ? Launch<float>::spmv_lean_interior(dv, (const float *)x, (float *)y, sf, 0,
                                                          wf, s, 0, nullptr, 0)
                      : Launch<float>::spmv_dot(dv, (const float *)x, (float *)y, sf, 0, wf, s);
-      if (split && (dv.variant & (2048 | 8192)))
+      if (split && sell_variant(dv.variant))
         return Launch<float>::spmv_dot_slices(dv, A->d_split, A->split_ni, 0, (const float *)x,
                                               (float *)y, sf, 0, wf, s);
       return Launch<float>::spmv_dot_variant(dv.variant, dv, (const float *)x, (float *)y, sf,
@@ -2759,7 +2750,7 @@ int autotune_spmv(cgx_csr *A) {
       return split ? Launch<double>::spmv_lean_interior(dv, (const double *)x, (double *)y, sd, 0,
                                                         wd, s, 0, nullptr, 0)
                    : Launch<double>::spmv_dot(dv, (const double *)x, (double *)y, sd, 0, wd, s);
-    if (split && (dv.variant & (2048 | 8192)))
+    if (split && sell_variant(dv.variant))
       return Launch<double>::spmv_dot_slices(dv, A->d_split, A->split_ni, 0, (const double *)x,
                                              (double *)y, sd, 0, wd, s);
     return Launch<double>::spmv_dot_variant(dv.variant, dv, (const double *)x, (double *)y, sd, wd,
@@ -2812,7 +2803,7 @@ int autotune_spmv(cgx_csr *A) {
   time_forms(forms, how, med);
   const float bnd_us = bnd_rows && e == hipSuccess ? med.back() : 0.0f;
   if (bnd_rows && e == hipSuccess) med.pop_back();
-  auto interior = [&](int v) { return split && (v & (2048 | 8192)); };
+  auto interior = [&](int v) { return split && sell_variant(v); };
   int best_v = 0;
   float best_us = 1e30f;
   if (e == hipSuccess) {
@@ -2834,7 +2825,7 @@ int autotune_spmv(cgx_csr *A) {
   // 95-99 against 103-104 us, isolated k_spmv_dot 58.6 against 54.2). The
   // march and its template form are therefore decided on their fd kernels
   // (the template form preferred).
-  if (e == hipSuccess && !split && A->dtype == CGX_F64 && (best_v & 2097152) &&
+  if (e == hipSuccess && !split && A->dtype == CGX_F64 && (best_v & kMarch) &&
       !(best_v & kVT) && A->dev.march_k > 0 && A->dev.march_a == 0 && A->dev.sl_t) {
     e = hipMalloc(&ap, nx * es);
     std::vector<CsrDev> fdf(2, A->dev);
@@ -2859,7 +2850,7 @@ int autotune_spmv(cgx_csr *A) {
   // per body, the p update inside the march's SpMV), which the lean walk's
   // mode 3 does not beat (4096^2: 4,983 against 5,187-5,372 it/s,
   // profiles/r04a_configs.log against r03p): it is not offered there.
-  const bool march2d = (best_v & 2097152) && A->dev.march_k > 0 && A->dev.march_a == 0;
+  const bool march2d = (best_v & kMarch) && A->dev.march_k > 0 && A->dev.march_a == 0;
   if (e == hipSuccess && A->dev.sl_t && !march2d && build_lean_classes(A, vtab) == CGX_OK &&
       !vtab.empty()) {
     const int G = lean_grid(A);
@@ -2919,8 +2910,8 @@ int autotune_spmv(cgx_csr *A) {
   }
   free_lean(A);
   A->dev.variant = best_v;
-  if (!(best_v & (2048 | 8192))) free_sell(A);
-  if (!(best_v & kC16) || (best_v & 8192)) free_col16(A);
+  if (!sell_variant(best_v)) free_sell(A);
+  if (!(best_v & kC16) || (best_v & kSellP)) free_col16(A);
   if (!(best_v & kIL)) free_il(A);
   return CGX_OK;
 }
@@ -3095,7 +3086,7 @@ static bool fd_auto(const cgx_cg *cg) {
   if (A->dist) return dist_fd_ok(A, cg->dtype) && A->dev.n <= (int64_t(4) << 20);
   if (cg->dtype != CGX_F64 || !Launch<double>::fd_supported(A->dev)) return false;
   const int v = launch_variant(A->dev, cg->dtype);
-  const bool march2d = (v & 2097152) && A->dev.march_a == 0;
+  const bool march2d = (v & kMarch) && A->dev.march_a == 0;
   const bool small = A->dev.nnz * (int64_t)(sizeof(double) + sizeof(int)) < (int64_t(64) << 20);
   // the lean walk with cache-resident vectors (<= 32 MB, stream_nt's bound):
   // the 256 x 256 x 32 slab 29.5-29.8 us per body in mode 4 against
@@ -3107,7 +3098,7 @@ static bool fd_auto(const cgx_cg *cg) {
   // 512^3 520 against 508 it/s, 548 with the fused walk's team form
   // (profiles/r05l_team_ab.log)
   const bool lean_big = vl_whole(A->dev) && A->dev.n >= (int64_t(32) << 20);
-  return march2d || (small && (v & 1048576)) || lean_cached || lean_big;
+  return march2d || (small && (v & kVcSt)) || lean_cached || lean_big;
 }
 
 // Auto mode picks 5 (the persistent body) for small single-device f64

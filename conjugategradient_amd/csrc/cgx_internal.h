@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "cgx_variant.h"
+
 namespace cgx {
 
 // ---- launch geometry --------------------------------------------------------
@@ -117,22 +119,17 @@ constexpr int kVc4Max = 15;  // 4-bit codes: 15 values, 0xf empty
 // its code word read from LDS instead of HBM. Its descriptor in the
 // template copy of the slice table (CsrDev::sl_t) carries t + 1 in the high
 // half of its width (widths are at most 64).
-constexpr int kVT = 8388608;
-// CSR-stream with 16-bit column deltas (bit 128 on the paired loop: 133 =
-// 5 | 128): 10 bytes per entry instead of 12
-constexpr int kC16 = 128;
+constexpr int kVtMax = 8;
+constexpr int kVtWidthMask = 0xffff;
 // CSR-stream on the interleaved copy of val / col (variant bit kIL on the
 // pipelined paired loop: 15 | kIL, 13 | kIL; round 6): the value pairs and
 // column pairs of each chunk of kIlCh consecutive pairs (2 kIlCh entries)
 // side by side in one array, kIlCh x 16 B of values then kIlCh x 8 B of
 // columns; the same 12 B per entry as the two CSR arrays, one stream instead
 // of two independently placed ones
-constexpr int kIL = 67108864;
 constexpr int kIlLog = 8;
 constexpr int kIlCh = 1 << kIlLog;          // pairs per chunk
 constexpr int64_t kIlChBytes = kIlCh * 24;  // 6 KiB (f64)
-constexpr int kVtMax = 8;
-constexpr int kVtWidthMask = 0xffff;
 // Lean stencil walk (variant bit kVL; DESIGN.md §4 "lean stencil walk"): a
 // slice whose offset pattern is a subset of a stencil's {-D, -a, -1, 0, +1,
 // +a, +D} (a = 0: the 2-D {-D, -1, 0, +1, +D}) and whose template chunk gives
@@ -145,7 +142,6 @@ constexpr int kVtWidthMask = 0xffff;
 // bit (v finite). Classes per slice: one byte, 0xff for the slices that run
 // the per-slice value-code form, laid out wave-major for the launch's grid
 // (row of wave w of XCD group g: (g step + w) * nst, step = grid / 2 waves).
-constexpr int kVL = 33554432;
 constexpr int kVlMaxCls = 32;
 struct VlClass {
   double v[8];      // value of canonical slot j: -D, -a, -1, 0, +1, +a, +D
@@ -200,16 +196,16 @@ struct CsrDev {
   int sell_kind = 0;
   const void *smask = nullptr;
   int64_t nx = 0;  // length of the gathered vector (n, + ghosts when partitioned)
-  // SELL-P value codes (variant bit 32768, null when the matrix has more
+  // SELL-P value codes (variant bit kVc, null when the matrix has more
   // than kVcMax distinct values): one byte per slot, index into svdict
   // (kVcAbsent: the row has no entry in the slot); layout at SellSlice.ioff
   const void *svc = nullptr;
   const void *svdict = nullptr;  // kVcDict values of the matrix's type
   int nvdict = 0;                // distinct values (0: no codes)
-  // 4-bit codes (variant bit 262144; at most kVc4Max values): 8 bytes per
+  // 4-bit codes (variant bit kVc4; at most kVc4Max values): 8 bytes per
   // lane per chunk, byte j = slot j, row 0 in the low nibble
   const void *svc4 = nullptr;
-  // plane march (variant bit 2097152; cgx_abi.cpp plan_march): the dominant
+  // plane march (variant bit kMarch; cgx_abi.cpp plan_march): the dominant
   // SELL-P pattern is {-D, (-a,) -1, 0, 1, (a,) D} with D = 128 march_k rows
   // at pool base march_pat; march_len: planes per run (0: fill the grid)
   int march_k = 0, march_a = 0, march_pat = -1, march_len = 0;
@@ -253,14 +249,14 @@ struct CsrDev {
   int ob_D = 0, ob_W = 0;
 };
 
-// The templates apply to the pipelined 4-bit value-code walks (bits 524288,
-// 262144; the consecutive walk and the plane march) of a matrix that has
+// The templates apply to the pipelined 4-bit value-code walks (bits kVcPipe,
+// kVc4; the consecutive walk and the plane march) of a matrix that has
 // them, when the requested variant asks for them: spmv_variant keeps kVT and
 // the kernel arguments take the template slice table under exactly this
 // condition.
 __host__ __device__ inline bool vt_active(const CsrDev &A) {
   return (A.variant & kVT) && A.sl_t && A.vct && A.nvt > 0 && A.svc4 && A.svc && A.sl &&
-         A.sell_kind && A.sell_maxw <= 8 && (A.variant & 524288) && (A.variant & 262144);
+         A.sell_kind && A.sell_maxw <= 8 && (A.variant & kVcPipe) && (A.variant & kVc4);
 }
 // the loop's k_spmv_dot is the lean walk (its generic slices run the
 // template value-code form, so vt_active holds too)
@@ -547,9 +543,6 @@ inline int64_t il_bytes(int64_t nnz, int es) {
 
 // the SpMV variant a launch on A uses (dtype: CGX_F64 / CGX_F32)
 int launch_variant(const CsrDev &A, int dtype);
-// a resolved variant that walks the CSR arrays (CSR-stream), not the SELL
-// (bit 2048) or SELL-P (bit 8192) copy
-inline bool csr_stream_variant(int v) { return (v & (2048 | 8192)) == 0; }
 // true when the variant A resolves to (launch_variant) has a k_spmv_dot
 // instantiation: a request that resolves to anything else would only fail
 // at its first launch

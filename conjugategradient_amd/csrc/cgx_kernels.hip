@@ -396,10 +396,10 @@ struct CsrArgs {
   int part_off;  // per launch: first partial slot of k_spmv_dot (split launches)
   const void *smask;  // SELL-P slot masks
   int64_t nx;         // gathered vector length
-  const void *svc;    // SELL-P value codes (variant bit 32768)
+  const void *svc;    // SELL-P value codes (variant bit kVc)
   const void *svdict; // their dictionary (kVcDict entries)
-  const void *svc4;   // 4-bit value codes (variant bit 262144)
-  // plane march (variant bit 2097152): slices a plane apart (0: no march
+  const void *svc4;   // 4-bit value codes (variant bit kVc4)
+  // plane march (variant bit kMarch): slices a plane apart (0: no march
   // pattern), the pattern's +-a offset (0: 2-D form), its pool base, and
   // the run length in planes (0: fill the grid)
   int mk, mo, mpat, ml;
@@ -433,14 +433,12 @@ __device__ __forceinline__ int block_at(const CsrArgs &A, int pos) {
   return A.rbo ? A.rbo[pos] : pos;
 }
 
-// Tile geometry of a variant: bit 64 selects half tiles (1024 entries /
-// 128 rows per row block) — fewer registers per thread, more workgroups per
-// CU to hide the gather latency. The matrix's row-block schedule must have
-// been built for the same tile (cgx_csr_set_tile).
+// Tile geometry of the CSR-stream forms: full tiles in every variant (a
+// row-block schedule built for smaller tiles, cgx_csr_set_tile, fits them).
 template <int V> struct TileOf {
-  static constexpr int tile = (V & 64) ? 1024 : 2048;
+  static constexpr int tile = kTile;
   static constexpr int cap = tile - 2;  // paired loads read up to 2 extra entries
-  static constexpr int rows = (V & 64) ? 128 : 256;
+  static constexpr int rows = kRowsPerBlock;
 };
 
 template <typename T, int TILE = kTile> struct SpmvLds {
@@ -670,7 +668,7 @@ template <typename T> struct GatherPL {
 template <int V>
 __device__ __forceinline__ void work_range(int nrb, int &first, int &step, int &end) {
   const int G = gridDim.x;
-  if ((V & 1) && (G & 7) == 0) {
+  if ((V & kXcd) && (G & 7) == 0) {
     const int g = blockIdx.x & 7, per = G >> 3;
     first = (int)(((int64_t)nrb * g) >> 3) + (blockIdx.x >> 3);
     end = (int)(((int64_t)nrb * (g + 1)) >> 3);
@@ -687,8 +685,8 @@ __device__ __forceinline__ void spmv_rows(const CsrArgs &A, const T *__restrict_
                                           const Gather &x, Epi &epi,
                                           SpmvLds<T, TileOf<V>::tile> &sm) {
   using TL = TileOf<V>;
-  constexpr bool NT = (V & 2) != 0;
-  constexpr bool PAIRS = (V & 4) != 0;
+  constexpr bool NT = (V & kNt) != 0;
+  constexpr bool PAIRS = (V & kPair) != 0;
   const int t = threadIdx.x;
   int first, step, end;
   work_range<V>(A.nrb, first, step, end);
@@ -795,7 +793,7 @@ __device__ __forceinline__ void spmv_rows_pipe(const CsrArgs &A, const T *__rest
                                                const Gather &x, Epi &epi,
                                                SpmvLds<T, TileOf<V>::tile> &sm) {
   using TL = TileOf<V>;
-  constexpr bool NT = (V & 2) != 0;
+  constexpr bool NT = (V & kNt) != 0;
   using PV = typename PairOf<T>::V;
   constexpr int U = TL::tile / (2 * kBlock);
   const int t = threadIdx.x;
@@ -849,7 +847,7 @@ __device__ __forceinline__ void spmv_rows_pipe(const CsrArgs &A, const T *__rest
     T g0[U], g1[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      if constexpr ((V & 16) != 0) {  // ablation (timing only): no gathers
+      if constexpr ((V & kAblG) != 0) {  // ablation (timing only): no gathers
         g0[u] = T(c[u].x & 1);
         g1[u] = T(c[u].y & 1);
       } else {
@@ -862,7 +860,7 @@ __device__ __forceinline__ void spmv_rows_pipe(const CsrArgs &A, const T *__rest
     Int2 cn[U];
     issue(nk0, nk1, vn, cn);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr ((V & 32) != 0) {  // ablation (timing only): no LDS / row phase
+    if constexpr ((V & kAblR) != 0) {  // ablation (timing only): no LDS / row phase
       T s = T(0);
 #pragma unroll
       for (int u = 0; u < U; ++u) s += v[u].x * g0[u] + v[u].y * g1[u];
@@ -923,7 +921,7 @@ __device__ __forceinline__ void spmv_rows_quad(const CsrArgs &A, const T *__rest
                                                const Gather &x, Epi &epi,
                                                SpmvLds<T, TileOf<V>::tile> &sm) {
   using TL = TileOf<V>;
-  constexpr bool NT = (V & 2) != 0;
+  constexpr bool NT = (V & kNt) != 0;
   using QV = typename QuadOf<T>::V;
   constexpr int U = TL::tile / (4 * kBlock);
   constexpr int CAP = TL::tile - 6;  // quads read up to 6 extra entries
@@ -1039,7 +1037,7 @@ __device__ __forceinline__ void spmv_rows_quad(const CsrArgs &A, const T *__rest
 // only): no gathers.
 // ---------------------------------------------------------------------------
 template <typename T> struct SellLds {
-  T vdict[kVcDict];  // value-code dictionary (variant bit 32768)
+  T vdict[kVcDict];  // value-code dictionary (variant bit kVc)
   unsigned long long vt[kVtMax * 64];  // value-code templates (variant bit kVT)
   T red[4 * kMaxRed];
   int flag;
@@ -1074,7 +1072,7 @@ __device__ __forceinline__ void sell_range(int nsl, int wg0, int &first, int &st
 // the last row) and are dropped at the add.
 template <typename T, int V, class Epi, class Gather>
 __device__ __forceinline__ void sell_slice(const CsrArgs &A, const Gather &x, Epi &epi, int s) {
-  constexpr bool NT = (V & 2) != 0;
+  constexpr bool NT = (V & kNt) != 0;
   const T *__restrict__ sval = static_cast<const T *>(A.sval);
   const int lane = threadIdx.x & 63;
   const SellSlice m = A.sl[s];
@@ -1095,7 +1093,7 @@ __device__ __forceinline__ void sell_slice(const CsrArgs &A, const Gather &x, Ep
     for (int j = 0; j < 8; ++j) {
       const unsigned k = (unsigned)(iw >> (8 * j)) & 0xffu;
       const int off = __builtin_amdgcn_ds_bpermute((int)(k << 2), dv);
-      if constexpr ((V & 16) != 0) g[j] = T(k & 1);
+      if constexpr ((V & kAblG) != 0) g[j] = T(k & 1);
       else g[j] = x(k != kSellPad ? row + off : rowc);
     }
 #pragma unroll
@@ -1133,7 +1131,7 @@ __device__ __forceinline__ void spmv_sell(const CsrArgs &A, const Gather &x, Epi
 // can be sunk past the prefetch); a partial last slice takes sell_slice.
 template <typename T, int V, class Epi, class Gather>
 __device__ __forceinline__ void spmv_sell_pipe(const CsrArgs &A, const Gather &x, Epi &epi) {
-  constexpr bool NT = (V & 2) != 0;
+  constexpr bool NT = (V & kNt) != 0;
   const T *__restrict__ sval = static_cast<const T *>(A.sval);
   const int lane = threadIdx.x & 63;
   int first, step, end, lo;
@@ -1170,7 +1168,7 @@ __device__ __forceinline__ void spmv_sell_pipe(const CsrArgs &A, const Gather &x
       for (int j = 0; j < 8; ++j) {
         const unsigned k = (unsigned)(iw >> (8 * j)) & 0xffu;
         const int off = __builtin_amdgcn_ds_bpermute((int)(k << 2), dv);
-        if constexpr ((V & 16) != 0) g[j] = T(k & 1);
+        if constexpr ((V & kAblG) != 0) g[j] = T(k & 1);
         else g[j] = x(k != kSellPad ? row + off : row);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -1201,7 +1199,7 @@ __device__ __forceinline__ void spmv_sell_pipe(const CsrArgs &A, const Gather &x
     if (s >= full) sell_slice<T, V, Epi, Gather>(A, x, epi, s);
 }
 
-// SELL with 2 rows per lane (variant bit 4096; slices of 128 rows): lane l
+// SELL with 2 rows per lane (variant bit kSell2; slices of 128 rows): lane l
 // owns rows 128 s + 2 l and + 1, so each value and index access is one
 // 16-byte load (two rows' slot j, two rows' index word) — half the load
 // instructions per row of the 1-row form, which streams at 8 bytes per lane.
@@ -1210,7 +1208,7 @@ __device__ __forceinline__ void spmv_sell_pipe(const CsrArgs &A, const Gather &x
 typedef unsigned long long Ull2 __attribute__((ext_vector_type(2)));
 template <typename T, int V, class Epi, class Gather>
 __device__ __forceinline__ void sell_slice2(const CsrArgs &A, const Gather &x, Epi &epi, int s) {
-  constexpr bool NT = (V & 2) != 0;
+  constexpr bool NT = (V & kNt) != 0;
   using PV = typename PairOf<T>::V;
   const PV *__restrict__ sval = static_cast<const PV *>(A.sval);
   const Ull2 *__restrict__ sidx = reinterpret_cast<const Ull2 *>(A.sidx);
@@ -1236,7 +1234,7 @@ __device__ __forceinline__ void sell_slice2(const CsrArgs &A, const Gather &x, E
       const unsigned k1 = (unsigned)(iw.y >> (8 * j)) & 0xffu;
       const int o0 = __builtin_amdgcn_ds_bpermute((int)(k0 << 2), dv);
       const int o1 = __builtin_amdgcn_ds_bpermute((int)(k1 << 2), dv);
-      if constexpr ((V & 16) != 0) {
+      if constexpr ((V & kAblG) != 0) {
         g0[j] = T(k0 & 1);
         g1[j] = T(k1 & 1);
       } else {
@@ -1265,7 +1263,7 @@ __device__ __forceinline__ void spmv_sell2(const CsrArgs &A, const Gather &x, Ep
     sell_slice2<T, V, Epi, Gather>(A, x, epi, slice_at(A, A.rev ? lo + end - 1 - s : s));
 }
 
-// SELL-P (variant bit 8192; 16384: u32 masks): the dictionary SELL layout
+// SELL-P (variant bit kSellP; kMask32: u32 masks): the dictionary SELL layout
 // with 2 rows per lane, but each slice stores its sorted offset pattern
 // o_0 < ... < o_{W-1} once (read as scalars) and every row a mask of the
 // slots it uses; values sit in pattern slots (zero where a row has no
@@ -1277,9 +1275,9 @@ __device__ __forceinline__ void spmv_sell2(const CsrArgs &A, const Gather &x, Ep
 // per row (1 or 4 bytes) instead of 8 bytes.
 template <typename T, int V, class Epi, class Gather>
 __device__ __forceinline__ void sellp_slice2(const CsrArgs &A, const Gather &x, Epi &epi, int s) {
-  constexpr bool NT = (V & 2) != 0;
+  constexpr bool NT = (V & kNt) != 0;
   using PV = typename PairOf<T>::V;
-  using MT = typename std::conditional<(V & 16384) != 0, unsigned, unsigned char>::type;
+  using MT = typename std::conditional<(V & kMask32) != 0, unsigned, unsigned char>::type;
   const PV *__restrict__ sval = static_cast<const PV *>(A.sval);
   const MT *__restrict__ smask = static_cast<const MT *>(A.smask);
   const auto *cs = (const __attribute__((address_space(4))) SellSlice *)A.sl;
@@ -1293,7 +1291,7 @@ __device__ __forceinline__ void sellp_slice2(const CsrArgs &A, const Gather &x, 
   const int rc0 = l0 ? r0 : (int)A.n - 1, rc1 = l1 ? r0 + 1 : (int)A.n - 1;
   epi.pre2(rc0, rc1);
   // both rows' masks in one load (r0 even; rows past n: mask 0, array padded)
-  using MT2 = typename std::conditional<(V & 16384) != 0, unsigned long long,
+  using MT2 = typename std::conditional<(V & kMask32) != 0, unsigned long long,
                                         unsigned short>::type;
   const MT2 mm = *reinterpret_cast<const MT2 *>(smask + r0);
   constexpr int MB = 8 * (int)sizeof(MT);
@@ -1311,7 +1309,7 @@ __device__ __forceinline__ void sellp_slice2(const CsrArgs &A, const Gather &x, 
       const int o = pat[pbase + min(c + j, W - 1)];
       const int base = r0 + o;
       const int cb = min(max(base, 0), nxm2);
-      if constexpr ((V & 16) != 0) {
+      if constexpr ((V & kAblG) != 0) {
         g0[j] = T(cb & 1);
         g1[j] = T(cb & 2);
       } else {
@@ -1341,7 +1339,7 @@ __device__ __forceinline__ void spmv_sellp(const CsrArgs &A, const Gather &x, Ep
     sellp_slice2<T, V, Epi, Gather>(A, x, epi, slice_at(A, A.rev ? lo + end - 1 - s : s));
 }
 
-// SELL-P with value codes (variant bit 32768 | 8192): the SELL-P slice walk
+// SELL-P with value codes (form kFVc = kSellP | kVc): the SELL-P slice walk
 // and pair gathers, but each slot's value comes from a 1-byte code into the
 // matrix's value dictionary (in LDS) instead of an 8-byte value, and the
 // code also says whether the row has an entry there (kVcAbsent), so no mask
@@ -1352,7 +1350,7 @@ template <typename T, int V, class Epi, class Gather>
 __device__ __forceinline__ void sellpv_slice2(const CsrArgs &A, const Gather &x, Epi &epi,
                                               const T *__restrict__ vd, int s,
                                               const unsigned long long *vt = nullptr) {
-  constexpr bool NT = (V & 2) != 0;
+  constexpr bool NT = (V & kNt) != 0;
   const Ull2 *__restrict__ codes = static_cast<const Ull2 *>(A.svc);
   const auto *cs = (const __attribute__((address_space(4))) SellSlice *)A.sl;
   const auto *pat = (const __attribute__((address_space(4))) int *)A.sdict;
@@ -1369,10 +1367,8 @@ __device__ __forceinline__ void sellpv_slice2(const CsrArgs &A, const Gather &x,
   epi.pre2(rc0, rc1);
   const int nxm2 = (int)A.nx - 2;
   T acc0 = T(0), acc1 = T(0);
-  // bit 131072: gather and sum the chunk in two halves of 4 slots (half the
-  // registers in flight)
-  constexpr int HS = (V & 131072) ? 4 : 8;
-  constexpr bool C4 = (V & 262144) != 0;  // 4-bit codes: one 8-byte word per lane
+  constexpr int HS = 8;  // slots gathered and summed together: the whole chunk
+  constexpr bool C4 = (V & kVc4) != 0;  // 4-bit codes: one 8-byte word per lane
   const unsigned long long *__restrict__ codes4 =
       static_cast<const unsigned long long *>(A.svc4);
   for (int c = 0; c < W; c += 8) {
@@ -1397,7 +1393,7 @@ __device__ __forceinline__ void sellpv_slice2(const CsrArgs &A, const Gather &x,
       const int o = pat[pbase + min(c + j, W - 1)];
       const int base = r0 + o;
       const int cb = min(max(base, 0), nxm2);
-      if constexpr ((V & 16) != 0) {
+      if constexpr ((V & kAblG) != 0) {
         g0[jj] = T(cb & 1);
         g1[jj] = T(cb & 2);
       } else {
@@ -1462,7 +1458,7 @@ template <> __device__ __forceinline__ float wave_shl1(float v, float edge) {
                                                     0x130, 0xf, 0xf, false));
 }
 
-// Software-pipelined value-code SELL-P (variant bit 524288; every slice at
+// Software-pipelined value-code SELL-P (variant bit kVcPipe; every slice at
 // most 8 wide, i.e. one code chunk): while slice s gathers and sums, the
 // next slice's descriptor and offset pattern (a dependent pair of scalar
 // loads) and its code word are in flight, so a slice's critical path is its
@@ -1471,9 +1467,9 @@ template <typename T, int V, class Epi, class Gather>
 __device__ __forceinline__ void spmv_sellpv_pipe(const CsrArgs &A, const Gather &x, Epi &epi,
                                                  const T *__restrict__ vd,
                                                  const unsigned long long *vt) {
-  constexpr bool NT = (V & 2) != 0;
-  constexpr bool C4 = (V & 262144) != 0;
-  constexpr bool CR = (V & 1048576) != 0;  // stencil slices: +-1 by lane shifts
+  constexpr bool NT = (V & kNt) != 0;
+  constexpr bool C4 = (V & kVc4) != 0;
+  constexpr bool CR = (V & kVcSt) != 0;  // stencil slices: +-1 by lane shifts
   const auto *cs = (const __attribute__((address_space(4))) SellSlice *)A.sl;
   const auto *pat = (const __attribute__((address_space(4))) int *)A.sdict;
   const Ull2 *__restrict__ codes = static_cast<const Ull2 *>(A.svc);
@@ -1538,7 +1534,7 @@ __device__ __forceinline__ void spmv_sellpv_pipe(const CsrArgs &A, const Gather 
     const int rc0 = l0 ? r0 : (int)A.n - 1, rc1 = l1 ? r0 + 1 : (int)A.n - 1;
     T g0[8], g1[8];
     const bool inner = inner_slice(si, o[0], o[7]);
-    // stencil slices (bit 1048576): offsets -1, 0, +1 in slots K..K+2 of a
+    // stencil slices (bit kVcSt): offsets -1, 0, +1 in slots K..K+2 of a
     // WW-wide pattern (K = 2, WW = 7: the 3-D 7-point interior; K = 1,
     // WW = 5: 2-D 5-point). The center pair x[r0], x[r0 + 1] is one aligned
     // load (and the dot's p); x[r0 - 1] and x[r0 + 2] come from the
@@ -1582,7 +1578,7 @@ __device__ __forceinline__ void spmv_sellpv_pipe(const CsrArgs &A, const Gather 
       const unsigned rb = (unsigned)r0 * (unsigned)sizeof(T);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        if constexpr ((V & 16) != 0) {
+        if constexpr ((V & kAblG) != 0) {
           g0[j] = T(rb & 1);
           g1[j] = T(rb & 2);
         } else {
@@ -1597,7 +1593,7 @@ __device__ __forceinline__ void spmv_sellpv_pipe(const CsrArgs &A, const Gather 
       for (int j = 0; j < 8; ++j) {
         const int base = r0 + o[j];
         const int cb = min(max(base, 0), nxm2);
-        if constexpr ((V & 16) != 0) {
+        if constexpr ((V & kAblG) != 0) {
           g0[j] = T(cb & 1);
           g1[j] = T(cb & 2);
         } else {
@@ -1648,7 +1644,7 @@ __device__ __forceinline__ void spmv_sellpv_pipe(const CsrArgs &A, const Gather 
   }
 }
 
-// Plane march (variant bit 2097152, on the pipelined stencil form 1875968):
+// Plane march (variant bit kMarch, on the pipelined stencil form kFVc4St):
 // for a matrix whose dominant slice pattern is {-D, -a, -1, 0, +1, +a, +D}
 // (3-D 7-point: a = nx, D = nx ny) or {-D, -1, 0, +1, +D} (2-D 5-point:
 // D = nx) with D a multiple of the 128-row slice (D = 128 K), a wave walks
@@ -1674,8 +1670,8 @@ template <typename T, int V, bool S3, class Epi, class Gather>
 __device__ __forceinline__ void spmv_sellpv_march(const CsrArgs &A, const Gather &x, Epi &epi,
                                                   const T *__restrict__ vd,
                                                   const unsigned long long *vt) {
-  constexpr bool NT = (V & 2) != 0;
-  constexpr bool C4 = (V & 262144) != 0;
+  constexpr bool NT = (V & kNt) != 0;
+  constexpr bool C4 = (V & kVc4) != 0;
   constexpr int H = 2 * kSellRows;
   using PV = typename PairU<T>::V;
   const Ull2 *__restrict__ codes = static_cast<const Ull2 *>(A.svc);
@@ -1754,7 +1750,7 @@ __device__ __forceinline__ void spmv_sellpv_march(const CsrArgs &A, const Gather
       b.cw = code_at(sl, io);
       const int fr = sl * H;
       const unsigned rb = (unsigned)min(fr + 2 * lane, nxm2) * (unsigned)sizeof(T);
-      if constexpr (S3 && (V & 16) != 0) {
+      if constexpr (S3 && (V & kAblG) != 0) {
         // bit 16 (timing ablation, spmv_dot only): no +-a gathers at all
         b.gm.x = b.gm.y = b.gp.x = b.gp.y = T(rb & 1);
       } else if constexpr (S3) {
@@ -1875,14 +1871,14 @@ __device__ __forceinline__ void spmv_sellpv(const CsrArgs &A, const Gather &x, E
   if constexpr ((V & kVT) != 0)  // the value-code templates next to the dictionary
     for (int i = threadIdx.x; i < A.nvt * 64; i += kBlock) vt[i] = A.vct[i];
   __syncthreads();
-  if constexpr ((V & 2097152) != 0) {
+  if constexpr ((V & kMarch) != 0) {
     if (A.mk > 0) {
       if (A.mo > 0) spmv_sellpv_march<T, V, true, Epi, Gather>(A, x, epi, vd, vt);
       else spmv_sellpv_march<T, V, false, Epi, Gather>(A, x, epi, vd, vt);
       return;
     }
   }
-  if constexpr ((V & 524288) != 0) {
+  if constexpr ((V & kVcPipe) != 0) {
     spmv_sellpv_pipe<T, V, Epi, Gather>(A, x, epi, vd, vt);
     return;
   }
@@ -1920,7 +1916,7 @@ template <typename T, class Epi, class Gather>
 __device__ __forceinline__ void spmv_lean(const CsrArgs &A, const Gather &x, Epi &epi,
                                           const T *__restrict__ vd,
                                           const unsigned long long *vt) {
-  constexpr int VG = 8192 | 32768 | 262144 | 524288 | kVT | 2;  // the generic slices' form
+  constexpr int VG = kFVc4PipeT | kNt;  // the generic slices' form
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // (the first A.wg0 workgroups of a launch with the halo push do that
@@ -2100,7 +2096,7 @@ template <typename T, class Epi, class Gather, bool PF = false>
 __device__ __forceinline__ void spmv_lean_team(const CsrArgs &A, const Gather &x, Epi &epi,
                                                const T *__restrict__ vd,
                                                const unsigned long long *vt, TeamLds<T> &tl) {
-  constexpr int VG = 8192 | 32768 | 262144 | 524288 | kVT | 2;  // the generic slices' form
+  constexpr int VG = kFVc4PipeT | kNt;  // the generic slices' form
   using PV = decltype(x.pair_b(0u));
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2306,19 +2302,19 @@ template <typename T> __device__ __forceinline__ T team_sum_parts(const T *part,
 template <typename T, int V> struct LdsSel { using type = SpmvLds<T, TileOf<V>::tile>; };
 template <typename T, int V>
 using LdsOf = typename std::conditional<
-    (V & (2048 | 8192)) != 0, SellLds<T>,
+    sell_variant(V), SellLds<T>,
     SpmvLds<T, TileOf<V>::tile>>::type;
 
 template <typename T, int V, class Epi, class Gather>
 __device__ __forceinline__ void spmv_any(const CsrArgs &A, const T *__restrict__ val,
                                          const Gather &x, Epi &epi, LdsOf<T, V> &sm) {
-  if constexpr ((V & 32768) != 0) spmv_sellpv<T, V, Epi, Gather>(A, x, epi, sm.vdict, sm.vt);
-  else if constexpr ((V & 8192) != 0) spmv_sellp<T, V, Epi, Gather>(A, x, epi);
-  else if constexpr ((V & 4096) != 0) spmv_sell2<T, V, Epi, Gather>(A, x, epi);
-  else if constexpr ((V & 2048) != 0 && (V & 8) != 0) spmv_sell_pipe<T, V, Epi, Gather>(A, x, epi);
-  else if constexpr ((V & 2048) != 0) spmv_sell<T, V, Epi, Gather>(A, x, epi);
-  else if constexpr ((V & 256) != 0) spmv_rows_quad<T, V, Epi, Gather>(A, val, x, epi, sm);
-  else if constexpr ((V & 8) != 0) spmv_rows_pipe<T, V, Epi, Gather>(A, val, x, epi, sm);
+  if constexpr ((V & kVc) != 0) spmv_sellpv<T, V, Epi, Gather>(A, x, epi, sm.vdict, sm.vt);
+  else if constexpr ((V & kSellP) != 0) spmv_sellp<T, V, Epi, Gather>(A, x, epi);
+  else if constexpr ((V & kSell2) != 0) spmv_sell2<T, V, Epi, Gather>(A, x, epi);
+  else if constexpr ((V & kSell) != 0 && (V & kPipe) != 0) spmv_sell_pipe<T, V, Epi, Gather>(A, x, epi);
+  else if constexpr ((V & kSell) != 0) spmv_sell<T, V, Epi, Gather>(A, x, epi);
+  else if constexpr ((V & kQuad) != 0) spmv_rows_quad<T, V, Epi, Gather>(A, val, x, epi, sm);
+  else if constexpr ((V & kPipe) != 0) spmv_rows_pipe<T, V, Epi, Gather>(A, val, x, epi, sm);
   else spmv_rows<T, V, Epi, Gather>(A, val, x, epi, sm);
 }
 
@@ -2743,15 +2739,13 @@ __global__ __launch_bounds__(kBlock) void k_cg_init(CsrArgs A, const T *__restri
 template <int V> struct SpmvWaves {
   // the plane march with templates: held to the 4 waves per SIMD (128
   // VGPRs, a 12-byte spill) the streamed-code march gets (it took 130 and 3)
-  static constexpr int w = (V & 32768) && (V & (65536 | 131072)) ? 8
-                           : ((V & kVT) && (V & 2097152)) ? 4
-                                                          : 1;
+  static constexpr int w = ((V & kVT) && (V & kMarch)) ? 4 : 1;
 };
 // k_spmv_fd: the same except the template march (held to 4 waves it
 // spilled 140 bytes; it takes 152 VGPRs, 3 waves, against 169 and 2 for the
 // streamed-code march)
 template <int V> struct FdWaves {
-  static constexpr int w = ((V & kVT) && (V & 2097152)) ? 1 : SpmvWaves<V>::w;
+  static constexpr int w = ((V & kVT) && (V & kMarch)) ? 1 : SpmvWaves<V>::w;
 };
 
 template <typename T, int V>
@@ -3266,7 +3260,7 @@ template <typename T, int Y, int M, int DIST, bool REV, class Epi, class Gather>
 __device__ __forceinline__ void spmv_lean_tile(const CsrArgs &A, const Gather &x, Epi &epi,
                                                const T *__restrict__ vd,
                                                const unsigned long long *vt, int zs) {
-  constexpr int VG = 8192 | 32768 | 262144 | 524288 | kVT | 2;  // the generic slices' form
+  constexpr int VG = kFVc4PipeT | kNt;  // the generic slices' form
   constexpr int NRC = DIST + 3;                 // center ring: planes i - 1 .. i + 1 + DIST
   constexpr int U = NRC % 2 ? 2 * NRC : NRC;    // unroll: both rings return to slot 0
   constexpr int NE = M < Y ? M : Y;             // outside +-a pairs per side
@@ -3631,7 +3625,7 @@ __device__ __forceinline__ void spmv_lean_ring(const CsrArgs &A, const Gather &x
                                                RingLds<T, W, Y> &rl) {
   static_assert(Y == M, "a wave owns one x-line: its +-a pairs are the next waves' centers");
   static_assert(W % (2 * Y) == 0 && 64 % (W / (2 * Y)) == 0, "halo slices split over the waves");
-  constexpr int VG = 8192 | 32768 | 262144 | 524288 | kVT | 2;  // the generic slices' form
+  constexpr int VG = kFVc4PipeT | kNt;  // the generic slices' form
   constexpr int NRC = DIST + 3;               // center ring: planes i - 1 .. i + 1 + DIST
   constexpr int U = NRC % 2 ? 2 * NRC : NRC;  // unroll (even: pub's parity is u mod 2)
   constexpr int HS = W / (2 * Y);             // waves per halo slice
@@ -4057,7 +4051,7 @@ __global__ __launch_bounds__(kBlock, FdWaves<V>::w) void k_spmv_fd(
       st->rxr[slot] = rr;
     }
   }
-  constexpr bool NTP = (V & 2097152) != 0;  // plane march: p_{k-1} lines read once
+  constexpr bool NTP = (V & kMarch) != 0;  // plane march: p_{k-1} lines read once
   const GatherP<T, NTP> g{r, pold, beta};
   EpiFD<T, NTP> e{Ap, pc, g, T(0), T(0), T(0)};
   spmv_any<T, V>(A, val, g, e, sm);
@@ -6328,37 +6322,40 @@ constexpr int64_t kNtMinBytes = int64_t(256) << 20;
 
 template <typename T> inline int spmv_variant(const CsrDev &A, int v = kSpmvV) {
   if (v < 0 && A.variant > 0) v = A.variant;  // chosen by cgx_csr_create's autotune
-  if (v >= 0 && (v & (2048 | 8192))) {
-    // the variant follows the SELL copy's layout: bit 4096 for 2 rows per
-    // lane; pipelined (bit 8) for 1 row per lane and slices <= 8 wide
-    if (A.sl && A.sell_kind && (v & 32768) && A.svc)
-      return 32768 | 8192 |
-             (v & (16 | 2 | 65536 | 131072 | (A.svc4 ? 262144 : 0) |
-                   (A.sell_maxw <= 8 ? 524288 | 1048576 : 0) |
-                   (A.sell_maxw <= 8 && A.march_k > 0 ? 2097152 : 0))) |
+  if (v >= 0 && sell_variant(v)) {
+    // the variant follows the SELL copy's layout: kSell2 for 2 rows per
+    // lane; pipelined (kPipe) for 1 row per lane and slices <= 8 wide
+    if (A.sl && A.sell_kind && (v & kVc) && A.svc)
+      return kFVc |
+             (v & (kAblG | kNt | (A.svc4 ? kVc4 : 0) |
+                   (A.sell_maxw <= 8 ? kVcPipe | kVcSt : 0) |
+                   (A.sell_maxw <= 8 && A.march_k > 0 ? kMarch : 0))) |
              (vt_active(A) ? kVT : 0);
-    if (A.sl && A.sell_kind) return 8192 | (A.sell_kind == 2 ? 16384 : 0) | (v & (16 | 2));
-    if (A.sl && A.sell_r == 2) return 2048 | 4096 | (v & (16 | 2));
-    if (A.sl) return v & (2048 | 16 | 2 | (A.sell_maxw <= 8 ? 8 : 0));
+    if (A.sl && A.sell_kind)
+      return kSellP | (A.sell_kind == 2 ? kMask32 : 0) | (v & (kAblG | kNt));
+    if (A.sl && A.sell_r == 2) return kFSell2 | (v & (kAblG | kNt));
+    if (A.sl) return v & (kSell | kAblG | kNt | (A.sell_maxw <= 8 ? kPipe : 0));
     v = -1;  // no SELL copy: CSR-stream
   }
-  if (v < 0) v = (A.nnz * int64_t(sizeof(T) + sizeof(int)) >= kNtMinBytes) ? 15 : 13;
-  // bits 16/32: timing ablations, only reachable through cgx_tune_spmv; the
-  // retired half-tile (64), three-stage (128) and wave-tile (512) bits drop
-  // (a schedule built for smaller tiles fits the full-tile kernels)
-  const bool c16 = (v & kC16) && A.col16 && (v & 4) && !(v & (8 | 256));
+  if (v < 0)
+    v = kCsrPipe | ((A.nnz * int64_t(sizeof(T) + sizeof(int)) >= kNtMinBytes) ? kNt : 0);
+  // kAblG / kAblR: timing ablations, only reachable through cgx_tune_spmv.
+  // kC16 and kIL are read here, before the mask, and put back below where
+  // they apply; every other bit outside kCsrBits drops
+  const bool c16 = (v & kC16) && A.col16 && (v & kPair) && !(v & (kPipe | kQuad));
   // the interleaved copy: the pipelined paired loop only (13 | kIL, 15 | kIL)
-  const bool il = (v & kIL) && A.il && (v & 12) == 12 && !(v & (256 | kC16)) && A.nnz >= 2;
-  v &= 1023 & ~(64 | 128 | 512);
+  const bool il = (v & kIL) && A.il && (v & (kPipe | kPair)) == (kPipe | kPair) &&
+                  !(v & (kQuad | kC16)) && A.nnz >= 2;
+  v &= kCsrBits;
   if (il) return v | kIL;
   if (((uintptr_t)A.val % (2 * sizeof(T))) || ((uintptr_t)A.col % 8) || A.nnz < 2)
     return 0;  // plain loads, no pipelining (any schedule with <= 2042-entry blocks)
   if (c16) return v | kC16;  // 132..135: paired loop, 16-bit column deltas
-  if ((v & 256) && (((uintptr_t)A.val % (4 * sizeof(T))) || ((uintptr_t)A.col % 16) ||
-                    A.nnz < 4))
-    v &= ~256;  // quads need 4-entry alignment
-  if (v & 256) return 256 | 8 | (v & 3);  // 264..267
-  if ((v & 8) && !(v & 4)) v &= ~8;  // the pipelined loop uses paired loads
+  if ((v & kQuad) && (((uintptr_t)A.val % (4 * sizeof(T))) || ((uintptr_t)A.col % 16) ||
+                      A.nnz < 4))
+    v &= ~kQuad;  // quads need 4-entry alignment
+  if (v & kQuad) return kCsrQuad | (v & (kXcd | kNt));  // 264..267
+  if ((v & kPipe) && !(v & kPair)) v &= ~kPipe;  // the pipelined loop uses paired loads
   return v;
 }
 
@@ -6370,74 +6367,19 @@ template <typename T> inline int spmv_variant(const CsrDev &A, int v = kSpmvV) {
   } while (0)
 
 // The SpMV forms k_spmv_dot is instantiated for (and cgx_csr_set_variant
-// accepts, cgx_abi.cpp known_variant): CSR-stream 0-7 (bits 1 XCD split, 2
-// non-temporal, 4 paired loads), 12-15 (+8 pipelined), 264-267 (quads);
-// dictionary SELL 2048/2050/2056/2058/6144/6146; SELL-P 8192/8194 (+16384:
-// 24576/24578); value-code SELL-P and its pipelined / stencil / plane-march
-// loops. (Round 1's half-tile, three-stage and wave-tile CSR forms and
-// round 3's row-gather form, negative results recorded in DESIGN.md §8, are
-// not built.) One-off
-// kernels (cg init, accuracy) run CSR-stream: every form gives the same
-// per-row sums.
-#define CGX_SPMV_SWITCH(v, KERNEL, ...)                        \
-  switch (v) {                                                 \
-    case 0: CGX_LAUNCH_V(KERNEL, 0, __VA_ARGS__);              \
-    case 1: CGX_LAUNCH_V(KERNEL, 1, __VA_ARGS__);              \
-    case 2: CGX_LAUNCH_V(KERNEL, 2, __VA_ARGS__);              \
-    case 3: CGX_LAUNCH_V(KERNEL, 3, __VA_ARGS__);              \
-    case 4: CGX_LAUNCH_V(KERNEL, 4, __VA_ARGS__);              \
-    case 5: CGX_LAUNCH_V(KERNEL, 5, __VA_ARGS__);              \
-    case 6: CGX_LAUNCH_V(KERNEL, 6, __VA_ARGS__);              \
-    case 7: CGX_LAUNCH_V(KERNEL, 7, __VA_ARGS__);              \
-    case 12: CGX_LAUNCH_V(KERNEL, 12, __VA_ARGS__);            \
-    case 13: CGX_LAUNCH_V(KERNEL, 13, __VA_ARGS__);            \
-    case 14: CGX_LAUNCH_V(KERNEL, 14, __VA_ARGS__);            \
-    case 15: CGX_LAUNCH_V(KERNEL, 15, __VA_ARGS__);            \
-    case 264: CGX_LAUNCH_V(KERNEL, 264, __VA_ARGS__);          \
-    case 265: CGX_LAUNCH_V(KERNEL, 265, __VA_ARGS__);          \
-    case 266: CGX_LAUNCH_V(KERNEL, 266, __VA_ARGS__);          \
-    case 267: CGX_LAUNCH_V(KERNEL, 267, __VA_ARGS__);          \
-    case 133: CGX_LAUNCH_V(KERNEL, 133, __VA_ARGS__);          \
-    case 67108877: CGX_LAUNCH_V(KERNEL, 67108877, __VA_ARGS__);\
-    case 67108879: CGX_LAUNCH_V(KERNEL, 67108879, __VA_ARGS__);\
-    case 135: CGX_LAUNCH_V(KERNEL, 135, __VA_ARGS__);          \
-    case 2048: CGX_LAUNCH_V(KERNEL, 2048, __VA_ARGS__);        \
-    case 2050: CGX_LAUNCH_V(KERNEL, 2050, __VA_ARGS__);        \
-    case 2056: CGX_LAUNCH_V(KERNEL, 2056, __VA_ARGS__);        \
-    case 2058: CGX_LAUNCH_V(KERNEL, 2058, __VA_ARGS__);        \
-    case 6144: CGX_LAUNCH_V(KERNEL, 6144, __VA_ARGS__);        \
-    case 6146: CGX_LAUNCH_V(KERNEL, 6146, __VA_ARGS__);        \
-    case 8192: CGX_LAUNCH_V(KERNEL, 8192, __VA_ARGS__);        \
-    case 8194: CGX_LAUNCH_V(KERNEL, 8194, __VA_ARGS__);        \
-    case 24576: CGX_LAUNCH_V(KERNEL, 24576, __VA_ARGS__);      \
-    case 24578: CGX_LAUNCH_V(KERNEL, 24578, __VA_ARGS__);      \
-    case 40960: CGX_LAUNCH_V(KERNEL, 40960, __VA_ARGS__);      \
-    case 40962: CGX_LAUNCH_V(KERNEL, 40962, __VA_ARGS__);      \
-    case 303104: CGX_LAUNCH_V(KERNEL, 303104, __VA_ARGS__);    \
-    case 303106: CGX_LAUNCH_V(KERNEL, 303106, __VA_ARGS__);    \
-    case 565248: CGX_LAUNCH_V(KERNEL, 565248, __VA_ARGS__);    \
-    case 565250: CGX_LAUNCH_V(KERNEL, 565250, __VA_ARGS__);    \
-    case 827392: CGX_LAUNCH_V(KERNEL, 827392, __VA_ARGS__);    \
-    case 827394: CGX_LAUNCH_V(KERNEL, 827394, __VA_ARGS__);    \
-    case 1613824: CGX_LAUNCH_V(KERNEL, 1613824, __VA_ARGS__);  \
-    case 1613826: CGX_LAUNCH_V(KERNEL, 1613826, __VA_ARGS__);  \
-    case 1875968: CGX_LAUNCH_V(KERNEL, 1875968, __VA_ARGS__);  \
-    case 1875970: CGX_LAUNCH_V(KERNEL, 1875970, __VA_ARGS__);  \
-    case 3710976: CGX_LAUNCH_V(KERNEL, 3710976, __VA_ARGS__);  \
-    case 3710978: CGX_LAUNCH_V(KERNEL, 3710978, __VA_ARGS__);  \
-    case 3973120: CGX_LAUNCH_V(KERNEL, 3973120, __VA_ARGS__);  \
-    case 3973122: CGX_LAUNCH_V(KERNEL, 3973122, __VA_ARGS__);  \
-    case 9216000: CGX_LAUNCH_V(KERNEL, 9216000, __VA_ARGS__);  \
-    case 9216002: CGX_LAUNCH_V(KERNEL, 9216002, __VA_ARGS__);  \
-    case 10264576: CGX_LAUNCH_V(KERNEL, 10264576, __VA_ARGS__);\
-    case 10264578: CGX_LAUNCH_V(KERNEL, 10264578, __VA_ARGS__);\
-    case 12361728: CGX_LAUNCH_V(KERNEL, 12361728, __VA_ARGS__);\
-    case 12361730: CGX_LAUNCH_V(KERNEL, 12361730, __VA_ARGS__);\
-    case 20750336: CGX_LAUNCH_V(KERNEL, 20750336, __VA_ARGS__);\
-    case 20750338: CGX_LAUNCH_V(KERNEL, 20750338, __VA_ARGS__);\
-    case 29138944: CGX_LAUNCH_V(KERNEL, 29138944, __VA_ARGS__);\
-    case 29138946: CGX_LAUNCH_V(KERNEL, 29138946, __VA_ARGS__);\
-    default: return hipErrorInvalidValue;                      \
+// accepts, cgx_abi.cpp known_variant) are CGX_SPMV_LIST (cgx_variant.h).
+// (Round 1's half-tile, three-stage and wave-tile CSR forms and round 3's
+// row-gather form, negative results recorded in DESIGN.md §8, are not
+// built.) One-off kernels (cg init, accuracy) run CSR-stream: every form
+// gives the same per-row sums.
+// CGX_SPMV_SWITCH launches k_spmv_dot in form v on the caller's a, p, Ap, st,
+// slot, ws and spmv_grid_: one case per form of the list.
+#define CGX_SPMV_DOT_CASE(VV) \
+  case VV: CGX_LAUNCH_V(k_spmv_dot, VV, a, (const T *)A.val, p, Ap, st, slot, ws);
+#define CGX_SPMV_SWITCH(v)                \
+  switch (v) {                            \
+    CGX_SPMV_LIST(CGX_SPMV_DOT_CASE)      \
+    default: return hipErrorInvalidValue; \
   }
 
 // Workgroups of k_spmv_dot<T, v> resident on the device at once (occupancy
@@ -6445,14 +6387,6 @@ template <typename T> inline int spmv_variant(const CsrDev &A, int v = kSpmvV) {
 // grid larger than what fits runs its last workgroups as a second wave,
 // after the first ones finish their fixed shares, and that tail measured
 // 8% of the value-code kernel at 256^3 (tools/gpu_vc_ab.sh).
-#define CGX_SPMV_LIST(X)                                                                    \
-  X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(12) X(13) X(14) X(15) X(264) X(265) X(266)      \
-  X(133) X(135) X(67108877) X(67108879)                                                     \
-  X(267) X(2048) X(2050) X(2056) X(2058) X(6144) X(6146) X(8192) X(8194) X(24576) X(24578)  \
-  X(40960) X(40962) X(303104) X(303106) X(565248) X(565250) X(827392) X(827394) X(1613824)  \
-  X(1613826) X(1875968) X(1875970) X(3710976) X(3710978) X(3973120) X(3973122)              \
-  X(9216000) X(9216002) X(10264576) X(10264578)                                             \
-  X(12361728) X(12361730) X(20750336) X(20750338) X(29138944) X(29138946)
 template <typename T> const void *spmv_dot_kernel(int v) {
   switch (v) {
 #define CGX_KP(VV) \
@@ -6498,12 +6432,13 @@ hipError_t Launch<T>::spmv(const CsrDev &A, const T *x, T *y, CgScalars<T> *st, 
 // One-off SpMV kernels (the init r = b - A x, accuracy()) run CSR-stream on
 // the caller's CSR arrays, whatever the loop's form: every form computes the
 // same per-row sums, and one launch per solve does not pay for an
-// instantiation per form. 13: pipelined paired loads (0 when val / col are
+// instantiation per form. kCsrPipe (13): pipelined paired loads (0 when val / col are
 // not aligned for them).
 #define CGX_CSR_ONEOFF(KERNEL, ...)                                             \
   do {                                                                          \
     const int spmv_grid_ = grid_rows(A.nrb);                                    \
-    if (spmv_variant<T>(A, 13) == 13) CGX_LAUNCH_V(KERNEL, 13, __VA_ARGS__);    \
+    if (spmv_variant<T>(A, kCsrPipe) == kCsrPipe)                            \
+      CGX_LAUNCH_V(KERNEL, kCsrPipe, __VA_ARGS__);                              \
     CGX_LAUNCH_V(KERNEL, 0, __VA_ARGS__);                                       \
   } while (0)
 template <typename T>
@@ -6573,17 +6508,17 @@ hipError_t Launch<T>::spmv_dot(const CsrDev &A, const T *p, T *Ap, CgScalars<T> 
     CGX_GGL(k_spmv_lean<T>, dim3(A.vl_grid), dim3(kBlock), 0, s, a, p, Ap, st, slot, ws);
     return hipGetLastError();
   }
-  if (A.sell_partial && (spmv_variant<T>(A) & (2048 | 8192))) {
+  if (A.sell_partial && sell_variant(spmv_variant<T>(A))) {
     // the SELL copy lacks the boundary rows: the whole matrix as CSR-stream
     CsrDev d = A;
-    d.variant = 13;
+    d.variant = kCsrPipe;
     d.lean = false;
     d.rbo = nullptr;
     return spmv_dot(d, p, Ap, st, slot, ws, s, rev);
   }
   const int v = spmv_variant<T>(A);
   const int spmv_grid_ = cap_resident<T>(grid_rows(A.nrb), v);
-  CGX_SPMV_SWITCH(v, k_spmv_dot, a, (const T *)A.val, p, Ap, st, slot, ws);
+  CGX_SPMV_SWITCH(v);
 }
 template <typename T>
 hipError_t Launch<T>::lean_dot(const CsrDev &A, const T *p, CgScalars<T> *st, int slot,
@@ -6659,20 +6594,20 @@ template <typename T>
 hipError_t Launch<T>::spmv_dot_slices(const CsrDev &A, const int *list, int count, int part_off,
                                       const T *p, T *Ap, CgScalars<T> *st, int slot,
                                       RedWs<T> *ws, hipStream_t s, int rev) {
-  const int v = spmv_variant<T>(A) & ~2097152;  // a slice list is walked in list order
-  if (!(v & (2048 | 8192)) || count < 1) return hipErrorInvalidValue;
+  const int v = spmv_variant<T>(A) & ~kMarch;  // a slice list is walked in list order
+  if (!sell_variant(v) || count < 1) return hipErrorInvalidValue;
   CsrArgs a = args(A);
   a.sorder = list;
   a.nsl = count;
   a.part_off = part_off;
   a.rev = rev;
   const int spmv_grid_ = slice_grid(A, count);
-  CGX_SPMV_SWITCH(v, k_spmv_dot, a, (const T *)A.val, p, Ap, st, slot, ws);
+  CGX_SPMV_SWITCH(v);
 }
 template <typename T> int Launch<T>::slice_grid(const CsrDev &A, int count) {
   const int g = (count + 3) / 4;  // one wave per slice, 4 waves per workgroup
   return cap_resident<T>(g < 1 ? 1 : (g > kMaxGrid ? kMaxGrid : g),
-                         spmv_variant<T>(A) & ~2097152);
+                         spmv_variant<T>(A) & ~kMarch);
 }
 template <typename T>
 hipError_t Launch<T>::spmv_dot_variant(int v, const CsrDev &A, const T *p, T *Ap,
@@ -6686,15 +6621,13 @@ hipError_t Launch<T>::spmv_dot_variant(int v, const CsrDev &A, const T *p, T *Ap
   }
   const int vv = spmv_variant<T>(A, v);
   const int spmv_grid_ = cap_resident<T>(grid_rows(A.nrb), vv);
-  switch (vv) {  // CSR-stream timing ablations (bits 16 / 32), tuning only
-    case 31: CGX_LAUNCH_V(k_spmv_dot, 31, args(A), (const T *)A.val, p, Ap, st, 0, ws);
-    case 47: CGX_LAUNCH_V(k_spmv_dot, 47, args(A), (const T *)A.val, p, Ap, st, 0, ws);
-    case 63: CGX_LAUNCH_V(k_spmv_dot, 63, args(A), (const T *)A.val, p, Ap, st, 0, ws);
-    case 67108927: CGX_LAUNCH_V(k_spmv_dot, 67108927, args(A), (const T *)A.val, p, Ap, st, 0, ws);
-    case 67108911: CGX_LAUNCH_V(k_spmv_dot, 67108911, args(A), (const T *)A.val, p, Ap, st, 0, ws);
+  const CsrArgs a = args(A);
+  constexpr int slot = 0;
+  switch (vv) {  // CSR-stream timing ablations (kAblG / kAblR), tuning only
+    CGX_ABLATION_LIST(CGX_SPMV_DOT_CASE)
     default: break;
   }
-  CGX_SPMV_SWITCH(vv, k_spmv_dot, args(A), (const T *)A.val, p, Ap, st, 0, ws);
+  CGX_SPMV_SWITCH(vv);
 }
 template <typename T>
 hipError_t Launch<T>::update_r(int64_t n, T *r, const T *Ap, CgScalars<T> *st, int slot,
@@ -6730,18 +6663,6 @@ hipError_t Launch<T>::update_r(int64_t n, T *r, const T *Ap, CgScalars<T> *st, i
 // the production SpMV forms only (CSR-stream, SELL-P, value-code SELL-P and
 // its pipelined / stencil / plane-march loops), f64 only; other variants
 // keep mode 3 (fd_supported).
-#define CGX_FD_LIST(X)                                                                 \
-  X(13) X(15) X(8192) X(8194) X(40960) X(40962) X(303104) X(303106) X(565248) X(565250) \
-  X(827392) X(827394) X(1613824) X(1613826) X(1875968) X(1875970) X(3710976) X(3710978) \
-  X(3973120) X(3973122) X(9216000) X(9216002) X(10264576) X(10264578) X(12361728)      \
-  X(12361730)
-
-// mode 2 (k_spmv_fused): mode 4's forms, plain CSR-stream and the
-// dictionary SELL forms small matrices take
-#define CGX_FUSED_LIST(X)                                                                \
-  CGX_FD_LIST(X) X(0) X(5) X(133) X(265) X(2048) X(2050) X(2056) X(2058) X(6144) X(6146) X(24576) \
-  X(24578)
-
 template <typename T> static const void *spmv_fd_kernel(int v) {
   if constexpr (!std::is_same<T, double>::value) {
     (void)v;
@@ -6823,11 +6744,6 @@ hipError_t Launch<T>::spmv_fd(const CsrDev &A, const T *r, const T *pold, T *pc,
 }
 // ---- the interior SpMV with the halo push in front (k_spmv_dot_push): the
 // SELL forms a partitioned matrix takes (no plane march: slice lists)
-#define CGX_PUSH_LIST(X)                                                                \
-  X(2048) X(2050) X(6144) X(6146) X(8192) X(8194) X(24576) X(24578) X(40960) X(40962)  \
-  X(303104) X(303106) X(565248) X(565250) X(827392) X(827394) X(1613824) X(1613826)     \
-  X(1875968) X(1875970) X(9216000) X(9216002) X(10264576) X(10264578)
-
 template <typename T> static const void *spmv_push_kernel(int v) {
   switch (v) {
 #define CGX_KPU(VV) \
@@ -6843,20 +6759,20 @@ template <typename T> static const void *spmv_bnd_kernel(int v) {
 #define CGX_KBN(VV) \
   case VV: return reinterpret_cast<const void *>(&k_spmv_dot_bnd<T, VV>);
     CGX_PUSH_LIST(CGX_KBN)
-    CGX_KBN(13) CGX_KBN(0)  // the boundary rows as CSR-stream blocks (spmv_dot_rows)
+    CGX_KBN(kCsrPipe) CGX_KBN(0)  // the boundary rows as CSR-stream blocks (spmv_dot_rows)
 #undef CGX_KBN
     default: return nullptr;
   }
 }
 template <typename T> bool Launch<T>::bnd_supported(const CsrDev &A) {
-  return spmv_bnd_kernel<T>(spmv_variant<T>(A) & ~2097152) != nullptr;
+  return spmv_bnd_kernel<T>(spmv_variant<T>(A) & ~kMarch) != nullptr;
 }
 template <typename T>
 hipError_t Launch<T>::spmv_dot_slices_bnd(const CsrDev &A, const int *list, int count,
                                           int part_off, const T *p, T *Ap, CgScalars<T> *st,
                                           int slot, RedWs<T> *ws, hipStream_t s, int rev,
                                           const PeerDev &P) {
-  const int v = spmv_variant<T>(A) & ~2097152;
+  const int v = spmv_variant<T>(A) & ~kMarch;
   const void *k = spmv_bnd_kernel<T>(v);
   if (!k || count < 1) return hipErrorInvalidValue;
   CsrArgs a = args(A);
@@ -6872,14 +6788,14 @@ hipError_t Launch<T>::spmv_dot_slices_bnd(const CsrDev &A, const int *list, int 
 }
 
 template <typename T> int Launch<T>::rows_grid(const CsrDev &A, int count) {
-  return cap_resident<T>(grid_rows(count), spmv_variant<T>(A, 13));
+  return cap_resident<T>(grid_rows(count), spmv_variant<T>(A, kCsrPipe));
 }
 template <typename T>
 hipError_t Launch<T>::spmv_dot_rows(const CsrDev &A, const int *blocks, int count, int part_off,
                                     const T *p, T *Ap, CgScalars<T> *st, int slot, RedWs<T> *ws,
                                     hipStream_t s, const PeerDev *P) {
-  const int v = spmv_variant<T>(A, 13);  // 13, or 0 for unaligned val / col
-  if (count < 1 || (v != 13 && v != 0)) return hipErrorInvalidValue;
+  const int v = spmv_variant<T>(A, kCsrPipe);  // kCsrPipe, or 0 for unaligned val / col
+  if (count < 1 || (v != kCsrPipe && v != 0)) return hipErrorInvalidValue;
   CsrArgs a = args(A);
   a.rbo = blocks;
   a.nrb = count;
@@ -6894,17 +6810,17 @@ hipError_t Launch<T>::spmv_dot_rows(const CsrDev &A, const int *blocks, int coun
     return cgx_lk(k, dim3(grid), dim3(kBlock), kargs, 0, s);
   }
   const int spmv_grid_ = grid;
-  if (v == 13) CGX_LAUNCH_V(k_spmv_dot, 13, a, val, p, Ap, st, slot, ws);
+  if (v == kCsrPipe) CGX_LAUNCH_V(k_spmv_dot, kCsrPipe, a, val, p, Ap, st, slot, ws);
   CGX_LAUNCH_V(k_spmv_dot, 0, a, val, p, Ap, st, slot, ws);
 }
 template <typename T> bool Launch<T>::push_supported(const CsrDev &A) {
-  return spmv_push_kernel<T>(spmv_variant<T>(A) & ~2097152) != nullptr;
+  return spmv_push_kernel<T>(spmv_variant<T>(A) & ~kMarch) != nullptr;
 }
 // SpMV workgroups of the pushing interior launch over `count` slices: the
 // interior launch's resident grid less the push workgroups (all resident)
 template <typename T> int Launch<T>::slice_grid_push(const CsrDev &A, int count, int wg0) {
   const int g = slice_grid(A, count);
-  const int r = spmv_dot_resident<T>(spmv_variant<T>(A) & ~2097152);
+  const int r = spmv_dot_resident<T>(spmv_variant<T>(A) & ~kMarch);
   const int cap = r > 0 ? r - wg0 : g;
   return std::max(1, std::min(g, cap));
 }
@@ -6913,7 +6829,7 @@ hipError_t Launch<T>::spmv_dot_slices_push(const CsrDev &A, const int *list, int
                                            int part_off, const T *p, T *Ap, CgScalars<T> *st,
                                            int slot, RedWs<T> *ws, hipStream_t s, int rev,
                                            const PeerDev &P, int wg0) {
-  const int v = spmv_variant<T>(A) & ~2097152;
+  const int v = spmv_variant<T>(A) & ~kMarch;
   const void *k = spmv_push_kernel<T>(v);
   if (!k || count < 1 || wg0 % 8) return hipErrorInvalidValue;
   CsrArgs a = args(A);
@@ -6984,16 +6900,16 @@ hipError_t Launch<T>::spmv_fd_rows_bnd(const CsrDev &A, const int *blocks, int c
   if constexpr (!std::is_same<T, double>::value) {
     return hipErrorInvalidValue;
   } else {
-    const int v = spmv_variant<T>(A, 13);  // 13, or 0 for unaligned val / col
-    if (count < 1 || (v != 13 && v != 0)) return hipErrorInvalidValue;
+    const int v = spmv_variant<T>(A, kCsrPipe);  // kCsrPipe, or 0 for unaligned val / col
+    if (count < 1 || (v != kCsrPipe && v != 0)) return hipErrorInvalidValue;
     CsrArgs a = args(A);
     a.rbo = blocks;
     a.nrb = count;
     a.part_off = part_off;
     const T *val = (const T *)A.val;
     const int grid = rows_grid(A, count);
-    if (v == 13)
-      CGX_GGL((k_spmv_fd_bnd<T, 13>), dim3(grid), dim3(kBlock), 0, s, a, val, r, pold, pc, Ap, st,
+    if (v == kCsrPipe)
+      CGX_GGL((k_spmv_fd_bnd<T, kCsrPipe>), dim3(grid), dim3(kBlock), 0, s, a, val, r, pold, pc, Ap, st,
               slot, ws, P);
     else
       CGX_GGL((k_spmv_fd_bnd<T, 0>), dim3(grid), dim3(kBlock), 0, s, a, val, r, pold, pc, Ap, st,
@@ -7023,8 +6939,8 @@ hipError_t Launch<T>::update_r_peer_rule(int64_t n, T *r, const T *Ap, CgScalars
 }
 template <typename T> int Launch<T>::spmv_parts(const CsrDev &A) {
   if (vl_whole(A)) return A.vl_grid;
-  if (A.sell_partial && (spmv_variant<T>(A) & (2048 | 8192)))  // spmv_dot's CSR-stream
-    return cap_resident<T>(grid_rows(A.nrb), spmv_variant<T>(A, 13));
+  if (A.sell_partial && sell_variant(spmv_variant<T>(A)))  // spmv_dot's CSR-stream
+    return cap_resident<T>(grid_rows(A.nrb), spmv_variant<T>(A, kCsrPipe));
   return cap_resident<T>(grid_rows(A.nrb), spmv_variant<T>(A));  // = spmv_dot's grid
 }
 template <typename T> int Launch<T>::update_parts(int64_t n) {

@@ -114,16 +114,16 @@ int cgx_csr_sell_info(cgx_csr *csr, int *has_sell, int64_t *padded_entries);
  * slices), 2 when a partitioned matrix's interior slice
  * list is, 0 for the natural order. */
 int cgx_csr_visit_order(cgx_csr *csr, int *ordered);
-/* Distinct values of the matrix's SELL-P value codes (variant bit 32768:
+/* Distinct values of the matrix's SELL-P value codes (variant bit 32768, kVc in cgx_variant.h:
  * one code byte per slot into a dictionary of at most 255 values, built by
  * cgx_csr_create when the SELL-P copy exists and the matrix has that few
  * distinct values; $CGX_VALUE_CODES=0 disables it), 0 when it has none. */
 int cgx_csr_value_codes(cgx_csr *csr, int *n_values);
-/* Value-code templates (variant bit 8388608): the number of distinct 4-bit
+/* Value-code templates (variant bit 8388608, kVT): the number of distinct 4-bit
  * code chunks stored once and read from LDS, and the slices that use one
  * (0 / 0: none). */
 int cgx_csr_templates(cgx_csr *csr, int *n_templates, int64_t *slices);
-/* The lean stencil walk (variant bit 33554432, kept by the autotune where it
+/* The lean stencil walk (variant bit 33554432, kVL; kept by the autotune where it
  * wins or requested with cgx_csr_set_variant): slices whose pattern is a
  * subset of one stencil's {-D, -a, -1, 0, +1, +a, +D} and whose template
  * chunk holds one value per slot, summed from per-class values with no
@@ -177,7 +177,7 @@ int cgx_csr_setup_times(cgx_csr *csr, double *ms, int cap, int *count);
  * (VectorOperations.hpp:438-466 has one SpMV form). */
 int cgx_csr_set_lean_team(cgx_csr *csr, int on);
 int cgx_csr_lean_team(cgx_csr *csr, int *on);
-/* The plane-march plan of the matrix's SELL-P copy (variant bit 2097152):
+/* The plane-march plan of the matrix's SELL-P copy (variant bit 2097152, kMarch):
  * *stride = slices (of 128 rows) between a slice and its +-D neighbour
  * (0: the dominant slice pattern is not a 7-point / 5-point stencil with D
  * a multiple of 128 rows, and the bit is ignored), *offset_a = the 3-D

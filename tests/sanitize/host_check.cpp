@@ -9,9 +9,15 @@
 //     row-block schedule (cgx_row_blocks) on Poisson, irregular, empty-row
 //     and single-row matrices;
 //   * the halo planners (cgx_plan_ghosts, cgx_plan_remap) on 1-D row
-//     partitions of those matrices at 1..5 ranks.
+//     partitions of those matrices at 1..5 ranks;
+//   * the SpMV variant resolution (launch_variant, launch_variant_ok,
+//     spmv_listed: pure host functions of a CsrDev) over a fixed grid of
+//     synthetic CsrDevs and a fixed request list, against the table
+//     <golden dir>/spmv_variant_table.txt recorded from the commit before
+//     the variant bits were named.
 // Any sanitizer report aborts with a non-zero exit; the test checks exit 0.
 //   host_check <golden dir> <tmp dir>
+//   host_check --dump-variants     the full resolution table, for a diff
 #include <cstdint>
 #include <cstdio>
 #include <algorithm>
@@ -20,6 +26,7 @@
 #include <vector>
 
 #include "cgx.h"
+#include "cgx_internal.h"
 
 #define EXPECT(c)                                                        \
   do {                                                                   \
@@ -132,7 +139,140 @@ static void plans(const Csr &m) {
   }
 }
 
+// ---- SpMV variant resolution ------------------------------------------------
+// The requests, as the public decimals (on purpose not the library's names):
+// every form the list held before the names, with the four retired y-march
+// numbers; the request forms cgx_csr_set_variant listed; the tuning
+// ablations; unknown and retired bits; the value-code forms with 2^24 set.
+static const int kRequests[] = {
+    0, 1, 2, 3, 4, 5, 6, 7, 12, 13, 14, 15, 264, 265, 266, 133, 135, 67108877, 67108879, 267,
+    2048, 2050, 2056, 2058, 6144, 6146, 8192, 8194, 24576, 24578, 40960, 40962, 303104, 303106,
+    565248, 565250, 827392, 827394, 1613824, 1613826, 1875968, 1875970, 3710976, 3710978,
+    3973120, 3973122, 9216000, 9216002, 10264576, 10264578, 12361728, 12361730,
+    20750336, 20750338, 29138944, 29138946,
+    34816, 34818, 296960, 296962, 559104, 559106, 821248, 821250, 1607680, 1607682, 1869824,
+    1869826, 9209856, 9209858, 10258434, 12355584, 12355586, 10258432,
+    31, 47, 63, 67108927, 67108911,
+    64, 512, 9999, 2138112,
+    16818176, 16818178, 17080320, 17080322, 17342464, 17342466, 17604608, 17604610, 18391040,
+    18391042, 18653184, 18653186, 20488192, 20488194, 25993216, 25993218, 27041792, 27041794};
+constexpr int kListed = 56;  // the leading entries: the list before the names
+static bool retired(int v) {
+  return v == 20750336 || v == 20750338 || v == 29138944 || v == 29138946;
+}
+
+struct VariantCfg {
+  int sl, kind, r, vc, maxw, march, tmpl, off;
+  long long nnz;
+  int f64;
+};
+
+// the configuration's line, its hash last; `full`: every (request,
+// resolved variant, has a kernel) after it
+static std::string variant_row(const VariantCfg &c, bool full) {
+  alignas(64) static char buf[256];
+  cgx::CsrDev A{};
+  A.n = 100;
+  A.nnz = c.nnz;
+  A.val = buf + c.off;
+  A.col = (const int *)(buf + 64 + c.off);
+  if (c.sl) {
+    A.sl = (const cgx::SellSlice *)buf;
+    A.sell_kind = c.kind;
+    A.sell_r = c.r;
+    A.svc = c.vc >= 1 ? buf : nullptr;
+    A.svc4 = c.vc >= 2 ? buf : nullptr;
+    A.sell_maxw = c.maxw;
+    A.march_k = c.march;
+    if (c.tmpl) {
+      A.sl_t = (const cgx::SellSlice *)buf;
+      A.vct = buf;
+      A.nvt = 2;
+    }
+  }
+  A.col16 = (const short *)buf;
+  A.il = buf;
+  A.lean = false;
+  const int dt = c.f64 ? CGX_F64 : CGX_F32;
+  uint64_t h = 14695981039346656037ull;  // FNV-1a, the two ints byte by byte
+  auto fold = [&](unsigned v) {
+    for (int b = 0; b < 4; ++b) h = (h ^ ((v >> (8 * b)) & 0xffu)) * 1099511628211ull;
+  };
+  std::string rest;
+  char t[64];
+  for (int q : kRequests) {
+    A.variant = q;
+    const int v = cgx::launch_variant(A, dt);
+    const int ok = cgx::launch_variant_ok(A, dt) ? 1 : 0;
+    fold((unsigned)v);
+    fold((unsigned)ok);
+    if (full) {
+      std::snprintf(t, sizeof t, " %d:%d:%d", q, v, ok);
+      rest += t;
+    }
+  }
+  char line[200];
+  std::snprintf(line, sizeof line,
+                "sl=%d kind=%d r=%d vc=%d maxw=%d march=%d tmpl=%d off=%d nnz=%lld %s %016llx",
+                c.sl, c.kind, c.r, c.vc, c.maxw, c.march, c.tmpl, c.off, c.nnz,
+                c.f64 ? "f64" : "f32", (unsigned long long)h);
+  return line + rest;
+}
+
+// the SELL fields (and the templates on them) count only when sl is set
+static std::vector<VariantCfg> variant_grid() {
+  std::vector<VariantCfg> g;
+  for (int sl : {0, 1})
+    for (int kind : {0, 1, 2})
+      for (int r : {1, 2})
+        for (int vc : {0, 1, 2})
+          for (int maxw : {7, 9})
+            for (int march : {0, 2})
+              for (int tmpl : {0, 1}) {
+                if (!sl && (kind != 0 || r != 1 || vc != 0 || maxw != 7 || march != 0 || tmpl))
+                  continue;
+                for (int off : {0, 8, 4})
+                  for (long long nnz : {1ll, 3ll, 1000ll})
+                    for (int f64 : {0, 1})
+                      g.push_back({sl, kind, r, vc, maxw, march, tmpl, off, nnz, f64});
+              }
+  return g;
+}
+
+static void variant_dump() {
+  for (const VariantCfg &c : variant_grid()) std::printf("%s\n", variant_row(c, true).c_str());
+}
+
+static void variant_table(const std::string &gold) {
+  for (int k = 0; k < (int)(sizeof kRequests / sizeof kRequests[0]); ++k) {
+    const int v = kRequests[k];
+    if (k < kListed) EXPECT(cgx::spmv_listed(v) == !retired(v));
+  }
+  std::FILE *f = std::fopen((gold + "/spmv_variant_table.txt").c_str(), "r");
+  EXPECT(f != nullptr);
+  char line[256];
+  size_t bad = 0, rows = 0;
+  for (const VariantCfg &c : variant_grid()) {
+    EXPECT(std::fgets(line, sizeof line, f) != nullptr);
+    std::string want = line;
+    while (!want.empty() && (want.back() == '\n' || want.back() == '\r')) want.pop_back();
+    ++rows;
+    if (variant_row(c, false) == want) continue;
+    if (++bad <= 10)
+      std::fprintf(stderr, "variant table: recorded %s\n  now %s\n", want.c_str(),
+                   variant_row(c, true).c_str());
+  }
+  EXPECT(std::fgets(line, sizeof line, f) == nullptr);  // no row left over
+  std::fclose(f);
+  if (bad) std::fprintf(stderr, "variant table: %zu of %zu rows differ\n", bad, rows);
+  EXPECT(bad == 0);
+}
+
 int main(int argc, char **argv) {
+  if (argc == 2 && std::string(argv[1]) == "--dump-variants") {
+    variant_dump();
+    return 0;
+  }
   if (argc < 3) return 2;
   const std::string gold = argv[1], tmp = argv[2];
   const char *files[] = {"poisson2d_16.mtx", "poisson2d_128.mtx", "poisson3d_16.mtx",
@@ -176,6 +316,7 @@ int main(int argc, char **argv) {
   plans(irregular(20000, 40, 1));
   plans(irregular(3000, 200, 2));
   plans(poisson(2, 1, 1, 1));
+  variant_table(gold);
   std::printf("host_check ok\n");
   return 0;
 }

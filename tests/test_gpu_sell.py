@@ -213,3 +213,38 @@ def test_auto_visit_order_on_large_planes(queue, oracle, monkeypatch):
     xr, res = oracle.cg_solve(rp, cl, vl, b, 0.0, max_iter=30)
     assert cg.iterations == res.iterations
     assert rel(cg.extract(), xr) <= 1e-12
+
+
+def test_retired_ymarch_numbers_are_refused(queue, oracle):
+    """The four y-march numbers (bit 2^24, removed with its kernel) have no
+    instantiated form: cgx_csr_set_variant refuses them as unknown and leaves
+    the matrix's variant alone. The plane march they used to resolve to
+    (3973122; 1875970 without a march plan) is still accepted and gives the
+    CSR-stream form's product bit for bit."""
+    rp, cl, vl = oracle.poisson(3, 16, 16, 16)   # SELL-P with 4-bit value codes
+    n = len(rp) - 1
+    A = Matrix(queue, vl, cl, rp)
+    assert _sell_info(A)[0] == 3
+    before, now = C.c_int(), C.c_int()
+    check(lib().cgx_csr_variant(A.schedule(), C.byref(before)))
+    for v in (20750336, 20750338, 29138944, 29138946):
+        assert lib().cgx_csr_set_variant(A.schedule(), v) != 0, v
+        assert "unknown SpMV variant" in lib().cgx_last_error().decode(), v
+        check(lib().cgx_csr_variant(A.schedule(), C.byref(now)))
+        assert now.value == before.value, v
+    stride, off_a, run = C.c_int(), C.c_int(), C.c_int()
+    check(lib().cgx_csr_march_info(A.schedule(), C.byref(stride), C.byref(off_a), C.byref(run)))
+    form = 3973122 if stride.value > 0 else 1875970
+    x = (np.arange(n) % 7 - 3).astype(np.float64)
+    ops = VectorOperations(queue)
+    ops.setVectorSize(n)
+    xv = Vector(queue, x)
+    outs = {}
+    for v in (13, form):
+        check(lib().cgx_csr_set_variant(A.schedule(), v))
+        check(lib().cgx_csr_variant(A.schedule(), C.byref(now)))
+        assert now.value == v
+        yv = Vector(queue, n)
+        ops.spmv(A, xv, yv, A.NNZ(), count=n)
+        outs[v] = yv.to_numpy()
+    np.testing.assert_array_equal(outs[form], outs[13])
