@@ -9,10 +9,10 @@ behind the interfaces of XeniaHerr/ConjugateGradient:
   Matrix-Market loader (test/mm_reader.cpp read_file) in ``.mtx``.
 """
 from ._native import CgxError, device_count, header_symbols, lib  # noqa: F401
-from .core import (CG, DeviceArray, Debuglevel, Event, Matrix, Preconditioner,  # noqa: F401
-                   Queue, Scalar, Vector, VectorOperations)
+from .core import (CG, DeviceArray, Debuglevel, Event, ManyCG, Matrix,  # noqa: F401
+                   Preconditioner, Queue, Scalar, Vector, VectorOperations)
 from .mtx import read_file, write_mtx_lower  # noqa: F401
 
-__all__ = ["CG", "CgxError", "Debuglevel", "DeviceArray", "Event", "Matrix", "Preconditioner",
-           "Queue", "Scalar", "Vector", "VectorOperations", "device_count", "header_symbols",
-           "lib", "read_file", "write_mtx_lower"]
+__all__ = ["CG", "CgxError", "Debuglevel", "DeviceArray", "Event", "ManyCG", "Matrix",
+           "Preconditioner", "Queue", "Scalar", "Vector", "VectorOperations", "device_count",
+           "header_symbols", "lib", "read_file", "write_mtx_lower"]

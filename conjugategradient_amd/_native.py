@@ -129,6 +129,12 @@ _SIGS = {
                                  C.POINTER(_i32)]),
     "cgx_mixed_inner": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "cgx_mixed_bytes": (_i32, [_vp, C.POINTER(_i64)]),
+    "cgx_many_create": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, C.POINTER(_vp)]),
+    "cgx_many_destroy": (_i32, [_vp]),
+    "cgx_many_config": (_i32, [_vp, _i32]),
+    "cgx_many_solve": (_i32, [_vp, _vp, _i64, _vp, _i64, _dbl, _i64, C.POINTER(_i64),
+                              C.POINTER(_dbl), C.POINTER(_i32)]),
+    "cgx_many_info": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)]),
     "cgx_accuracy": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_dbl)]),
     "cgx_poisson_nnz": (_i64, [_i32, _i32, _i32, _i32, _i64, _i64]),
     "cgx_poisson_fill": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),

@@ -679,3 +679,111 @@ class CG:
             self._drop_solver()
         except Exception:
             pass
+
+
+class ManyCG:
+    """Extension (cgx_many): ``nsys`` small SPD systems on one
+    sparsity pattern, each solved by one workgroup that runs the whole CG loop.
+
+    ``rows`` (n + 1) and ``cols`` (nnz) are the shared CSR pattern, ``vals``
+    (nsys, nnz) each system's values; n <= 4096, float64. Every system's
+    result is the single solve's in mode 1, bit for bit (cgx.h). ValueError /
+    TypeError, before any device call, for a float32 ``vals``, a shape that
+    does not fit, n outside 1..4096 or a malformed ``rows``. ``set_values``
+    overwrites the values in place for the next solve (no new create)."""
+
+    MAX_N = 4096
+
+    def __init__(self, queue: Queue, rows, cols, vals, max_workgroups: int = 0):
+        vals = np.asarray(vals)
+        if vals.dtype == np.float32:
+            raise TypeError("ManyCG solves float64 systems; vals is float32")
+        if vals.ndim != 2:
+            raise ValueError(f"vals must be a 2-D (nsys, nnz) array, got {vals.ndim} dimension(s)")
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        nsys, nnz = vals.shape
+        n = len(rows) - 1
+        if nsys < 1:
+            raise ValueError("vals holds no system (nsys must be at least 1)")
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError(f"a system has 1 to {self.MAX_N} rows, got {n}; solve larger "
+                             "systems one at a time with CG.solve")
+        if len(cols) != nnz:
+            raise ValueError(f"cols has {len(cols)} entries, vals {nnz} per system")
+        if rows[0] != 0 or rows[-1] != nnz:
+            raise ValueError(f"rows must run from 0 to nnz = {nnz}, got {rows[0]} .. {rows[-1]}")
+        if int(max_workgroups) < 0:
+            raise ValueError(f"max_workgroups {max_workgroups!r} must not be negative")
+        self._queue = queue
+        self.nsys, self.n, self.nnz = nsys, n, nnz
+        self.bodies = self.rxr = self.stopped = None
+        self._h = None
+        self._rows = DeviceArray(queue, n + 1, np.int32).upload(rows)
+        self._cols = DeviceArray(queue, nnz, np.int32).upload(cols)
+        self._vals = DeviceArray(queue, nsys * nnz, np.float64).upload(
+            np.asarray(vals, dtype=np.float64).ravel())
+        h = _vp()
+        check(lib().cgx_many_create(queue.handle, N.F64, nsys, n, nnz, self._rows.ptr,
+                                    self._cols.ptr, self._vals.ptr, nnz, C.byref(h)))
+        self._h = h
+        if max_workgroups:
+            self.config(max_workgroups)
+
+    def config(self, max_workgroups: int = 0) -> None:
+        """Cap the grid (0: the resident workgroups); a tuning knob."""
+        check(lib().cgx_many_config(self._h, int(max_workgroups)))
+
+    def info(self):
+        """(workgroups of the next solve, rows per thread, LDS bytes per workgroup)"""
+        wg, r, lds = C.c_int(0), C.c_int(0), C.c_int64(0)
+        check(lib().cgx_many_info(self._h, C.byref(wg), C.byref(r), C.byref(lds)))
+        return wg.value, r.value, lds.value
+
+    def set_values(self, vals) -> None:
+        """Overwrite every system's values in place; the next solve reads them."""
+        vals = np.asarray(vals, dtype=np.float64)
+        if vals.shape != (self.nsys, self.nnz):
+            raise ValueError(f"vals has shape {vals.shape}, expected {(self.nsys, self.nnz)}")
+        self._vals.upload(vals.ravel())
+
+    def solve(self, B, X0=None, improvement: float = 0.0, max_iter: int = -1) -> np.ndarray:
+        """Solve A_s x_s = b_s for every s: ``B`` (nsys, n), ``X0`` the initial
+        guesses (same shape; default 0). ``improvement`` is the absolute
+        tolerance on sqrt(r.r) and ``max_iter`` caps the bodies (-1: n + 1), as
+        CG.solve's. Returns X (nsys, n) and sets ``bodies``, ``rxr`` (the r.r
+        after each system's last body) and ``stopped`` (1 stop rule or NaN,
+        2 cap). ValueError, before any device call, for a wrong shape."""
+        B = np.asarray(B)
+        if B.shape != (self.nsys, self.n):
+            raise ValueError(f"B has shape {B.shape}, expected {(self.nsys, self.n)}")
+        if X0 is not None:
+            X0 = np.asarray(X0)
+            if X0.shape != B.shape:
+                raise ValueError(f"X0 has shape {X0.shape}, B {B.shape}")
+        ns, n = self.nsys, self.n
+        dB = DeviceArray(self._queue, ns * n, np.float64).upload(
+            np.asarray(B, dtype=np.float64).ravel())
+        dX = DeviceArray(self._queue, ns * n, np.float64)
+        if X0 is None:
+            dX.fill(0.0)
+        else:
+            dX.upload(np.asarray(X0, dtype=np.float64).ravel())
+        bodies, rxr, stopped = (C.c_int64 * ns)(), (C.c_double * ns)(), (C.c_int * ns)()
+        check(lib().cgx_many_solve(self._h, dB.ptr, n, dX.ptr, n, float(improvement),
+                                   int(max_iter), bodies, rxr, stopped))
+        self.bodies = np.array(bodies[:], dtype=np.int64)
+        self.rxr = np.array(rxr[:], dtype=np.float64)
+        self.stopped = np.array(stopped[:], dtype=np.int32)
+        return dX.download().reshape(ns, n)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().cgx_many_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass

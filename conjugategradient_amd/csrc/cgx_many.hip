@@ -1,0 +1,436 @@
+// cgx_many.hip — many small SPD systems on one sparsity pattern (cgx.h
+// "cgx_many"): one workgroup of kBlock threads runs a whole CG
+// solve, init and every body, then takes the next system. Thread t owns rows
+// t, t + 256, ...: their x and r stay in registers, p (the gather source)
+// lives in LDS, a dot is a workgroup reduction. There is no kernel boundary,
+// no graph replay and no traffic between workgroups; the body loop is bounded
+// by the cap (at most n + 1 <= 4,097 bodies), so a workgroup always ends.
+//
+// Arithmetic (normative; cgx.h): system s's x, body count, stop code and final
+// r.r are those of cgx_cg_solve in mode 1 on (rowptr, col, val_s), bit for
+// bit: the single kernels' per-element expressions with products rounded
+// before adds (-ffp-contract=off), a row summed by one thread from 0 in
+// ascending entry order, the dots double-length sums (cgx_dd.h) rounded once,
+// stop rule Q5 as k_update_xp applies it.
+#include <cmath>
+#include <climits>
+#include <map>
+#include <mutex>
+
+#include "cgx_dd.h"
+#include "cgx_objects.h"
+
+using namespace cgx;
+
+namespace {
+
+struct DeviceGuard {
+  explicit DeviceGuard(int dev) { (void)hipSetDevice(dev); }
+};
+
+constexpr int kManyMaxN = 16 * kBlock;  // rows of one system: the widest instantiation's
+
+struct ManyArgs {
+  const int *rowptr, *col;
+  const double *val, *B;
+  double *X;
+  int64_t ldv, ldb, ldx;
+  long long *bodies;  // per system: the outputs
+  double *rxr;
+  int *stopped;
+  double tol;
+  int nsys, n, cap;
+};
+
+// The workgroup sum of one pair per thread, rounded once, in every thread:
+// waves first (wave_sum_dd), then wave 0 to 3 in that order, as
+// mx_block_sum (cgx_mixed.hip). red: 8 doubles that no thread writes again
+// before the workgroup's next barrier but one (the callers alternate two).
+__device__ __forceinline__ double many_sum(Dd<double> v, double *red) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  v = wave_sum_dd(v);
+  if (lane == 0) {
+    red[2 * w] = v.hi;
+    red[2 * w + 1] = v.lo;
+  }
+  __syncthreads();
+  Dd<double> s(red[0], red[1]);
+#pragma unroll
+  for (int k = 1; k < kBlock / 64; ++k) s += Dd<double>(red[2 * k], red[2 * k + 1]);
+  return s.value();
+}
+
+// R rows per thread: n <= R kBlock. LDS: p (R kBlock doubles) and two
+// reduction stagings.
+template <int R>
+__global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
+  __shared__ double p[R * kBlock];
+  __shared__ double red[2][8];
+  const int t = threadIdx.x, n = a.n;
+  // the pattern is every system's: a thread's row bounds stay in registers
+  int e0[R], e1[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    const int i = t + k * kBlock;
+    e0[k] = i < n ? a.rowptr[i] : 0;
+    e1[k] = i < n ? a.rowptr[i + 1] : 0;
+  }
+  for (int s = blockIdx.x; s < a.nsys; s += gridDim.x) {
+    const double *__restrict__ val = a.val + (int64_t)s * a.ldv;
+    const double *__restrict__ b = a.B + (int64_t)s * a.ldb;
+    double *__restrict__ xs = a.X + (int64_t)s * a.ldx;
+    double x[R], r[R];
+    // ---- init: r = b - A x, p = r, rxr = r.r (k_cg_init) ----
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = t + k * kBlock;
+      x[k] = i < n ? xs[i] : 0.0;
+      if (i < n) p[i] = x[k];  // x through LDS: the init's gather source
+    }
+    __syncthreads();
+    Dd<double> acc(0.0);
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = t + k * kBlock;
+      double sum = 0.0;
+      for (int e = e0[k]; e < e1[k]; ++e) sum = sum + val[e] * p[a.col[e]];
+      r[k] = 0.0;
+      if (i < n) {
+        r[k] = b[i] - sum;
+        acc += r[k] * r[k];
+      }
+    }
+    __syncthreads();  // every gather of x is done: p may be overwritten
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = t + k * kBlock;
+      if (i < n) p[i] = r[k];
+    }
+    double rxr = many_sum(acc, red[1]);  // (its barrier publishes p too)
+    long long bodies = 0;
+    int stopped = 0;
+    // ---- the bodies ----
+    for (;;) {
+      // Ap = A p and p.Ap (k_spmv_dot)
+      double Ap[R];
+      acc = Dd<double>(0.0);
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = t + k * kBlock;
+        double sum = 0.0;
+        for (int e = e0[k]; e < e1[k]; ++e) sum = sum + val[e] * p[a.col[e]];
+        Ap[k] = sum;
+        if (i < n) acc += sum * p[i];
+      }
+      const double pAp = many_sum(acc, red[0]);
+      const double alpha = rxr / pAp;
+      // r -= alpha Ap and r.r (k_update_r)
+      acc = Dd<double>(0.0);
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = t + k * kBlock;
+        if (i < n) {
+          r[k] = r[k] - alpha * Ap[k];
+          acc += r[k] * r[k];
+        }
+      }
+      const double rr = many_sum(acc, red[1]);
+      const double beta = rr / rxr;
+      // x += alpha p; p = r + beta p; the stop rule (k_update_xp). Every
+      // gather of this body's p lies before the two barriers above.
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = t + k * kBlock;
+        if (i < n) {
+          const double pv = p[i];
+          x[k] = x[k] + alpha * pv;
+          p[i] = r[k] + beta * pv;
+        }
+      }
+      ++bodies;
+      const bool cond = isnan(rxr) || sqrt(rxr) <= a.tol;  // Q5: the r.r the body began with
+      const bool cont = !cond && bodies < a.cap;
+      stopped = cond ? 1 : (cont ? 0 : 2);
+      rxr = rr;
+      __syncthreads();  // the new p, before the next gather (or the next system's x)
+      if (!cont) break;
+    }
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = t + k * kBlock;
+      if (i < n) xs[i] = x[k];
+    }
+    if (t == 0) {
+      a.bodies[s] = bodies;
+      a.rxr[s] = rxr;
+      a.stopped[s] = stopped;
+    }
+  }
+}
+
+// The pattern's check, once at create: bad[0] counts the entries of rowptr
+// that are outside [0, nnz], descend, or miss rowptr[0] = 0 / rowptr[n] = nnz,
+// bad[1] the columns outside [0, n).
+__global__ __launch_bounds__(kBlock) void k_many_check(int n, int nnz,
+                                                       const int *__restrict__ rowptr,
+                                                       const int *__restrict__ col,
+                                                       unsigned long long *bad) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  unsigned long long br = 0, bc = 0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= n; i += stride) {
+    const int v = rowptr[i];
+    if (v < 0 || v > nnz) ++br;
+    else if (i == 0 && v != 0) ++br;
+    else if (i == n && v != nnz) ++br;
+    else if (i > 0 && rowptr[i - 1] > v) ++br;
+  }
+  for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < nnz; e += stride) {
+    const int c = col[e];
+    if (c < 0 || c >= n) ++bc;
+  }
+  if (br) atomicAdd(&bad[0], br);
+  if (bc) atomicAdd(&bad[1], bc);
+}
+
+int many_rows_per_thread(int64_t n) {
+  int r = 1;
+  while ((int64_t)r * kBlock < n) r *= 2;
+  return r;
+}
+
+const void *many_kernel(int r) {
+  switch (r) {
+    case 1: return reinterpret_cast<const void *>(&k_many_cg<1>);
+    case 2: return reinterpret_cast<const void *>(&k_many_cg<2>);
+    case 4: return reinterpret_cast<const void *>(&k_many_cg<4>);
+    case 8: return reinterpret_cast<const void *>(&k_many_cg<8>);
+    case 16: return reinterpret_cast<const void *>(&k_many_cg<16>);
+    default: return nullptr;
+  }
+}
+
+// workgroups of k_many_cg<r> resident on the device at once (occupancy x
+// CUs; 0: unknown), as spmv_dot_resident
+int many_resident(int r) {
+  static std::mutex mu;
+  static std::map<std::pair<int, int>, int> cache;  // (device, r) -> workgroups
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find({dev, r});
+  if (it != cache.end()) return it->second;
+  int res = 0, nb = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, many_kernel(r), kBlock, 0) == hipSuccess &&
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
+    res = nb * cus;
+  cache[{dev, r}] = res;
+  return res;
+}
+
+}  // namespace
+
+struct cgx_many {
+  cgx_ctx *ctx = nullptr;
+  int64_t nsys = 0, n = 0, nnz = 0, ldv = 0;
+  const int *rowptr = nullptr, *col = nullptr;  // the caller's
+  const double *val = nullptr;
+  int r = 1;               // rows per thread
+  int max_workgroups = 0;  // cgx_many_config (0: the resident workgroups)
+  long long *d_bodies = nullptr;
+  double *d_rxr = nullptr;
+  int *d_stopped = nullptr;
+  long long *h_bodies = nullptr;  // pinned, nsys each
+  double *h_rxr = nullptr;
+  int *h_stopped = nullptr;
+};
+
+namespace {
+
+void many_free(cgx_many *m) {
+  if (!m) return;
+  void *dev[] = {m->d_bodies, m->d_rxr, m->d_stopped};
+  for (void *p : dev)
+    if (p) (void)hipFree(p);
+  void *host[] = {m->h_bodies, m->h_rxr, m->h_stopped};
+  for (void *p : host)
+    if (p) (void)hipHostFree(p);
+  if (m->ctx) ctx_release(m->ctx);
+  delete m;
+}
+
+int many_grid(const cgx_many *m) {
+  int64_t g = m->nsys;
+  const int res = many_resident(m->r);
+  if (res > 0) g = std::min<int64_t>(g, res);
+  if (m->max_workgroups > 0) g = std::min<int64_t>(g, m->max_workgroups);
+  return (int)std::min<int64_t>(std::max<int64_t>(g, 1), INT_MAX);
+}
+
+}  // namespace
+
+extern "C" int cgx_many_create(cgx_ctx *ctx, int dtype, int64_t nsys, int64_t n, int64_t nnz,
+                               const int32_t *d_rowptr, const int32_t *d_col, const void *d_val,
+                               int64_t ldv, cgx_many **out) {
+  CGX_REQUIRE(out, CGX_EINVAL, "cgx_many_create: out is NULL");
+  *out = nullptr;
+  CGX_REQUIRE(dtype == CGX_F64 || dtype == CGX_F32, CGX_EINVAL,
+              "cgx_many_create: unknown dtype %d", dtype);
+  CGX_REQUIRE(dtype == CGX_F64, CGX_EUNSUPPORTED,
+              "cgx_many_create: f32 systems are not supported (the many-systems solve is f64)");
+  CGX_REQUIRE(nsys >= 1, CGX_EINVAL, "cgx_many_create: nsys %lld must be at least 1",
+              (long long)nsys);
+  CGX_REQUIRE(nsys <= INT_MAX, CGX_EINVAL, "cgx_many_create: nsys %lld exceeds %d",
+              (long long)nsys, INT_MAX);
+  CGX_REQUIRE(n >= 1, CGX_EINVAL, "cgx_many_create: n %lld must be at least 1", (long long)n);
+  CGX_REQUIRE(n <= kManyMaxN, CGX_EUNSUPPORTED,
+              "cgx_many_create: n %lld exceeds %d rows, the most one workgroup holds; solve "
+              "larger systems one at a time with cgx_cg_solve",
+              (long long)n, kManyMaxN);
+  CGX_REQUIRE(nnz >= 0 && nnz <= INT_MAX, CGX_EINVAL,
+              "cgx_many_create: nnz %lld is outside [0, %d]", (long long)nnz, INT_MAX);
+  CGX_REQUIRE(ldv >= nnz, CGX_EINVAL, "cgx_many_create: ldv %lld is below nnz %lld",
+              (long long)ldv, (long long)nnz);
+  CGX_REQUIRE((((uintptr_t)d_rowptr | (uintptr_t)d_col) & 3) == 0, CGX_EINVAL,
+              "cgx_many_create: rowptr and col must be 4-byte aligned");
+  CGX_REQUIRE(((uintptr_t)d_val & 7) == 0, CGX_EINVAL,
+              "cgx_many_create: the values must be 8-byte aligned");
+  // (last, so that the refusals above need no device)
+  CGX_REQUIRE(ctx && d_rowptr && d_col && d_val, CGX_EINVAL, "cgx_many_create: NULL argument");
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  auto *m = new cgx_many();
+  m->ctx = ctx;
+  ctx_retain(ctx);
+  m->nsys = nsys;
+  m->n = n;
+  m->nnz = nnz;
+  m->ldv = ldv;
+  m->rowptr = d_rowptr;
+  m->col = d_col;
+  m->val = (const double *)d_val;
+  m->r = many_rows_per_thread(n);
+  unsigned long long *bad = nullptr, h[2] = {0, 0};
+  hipError_t e = hipMalloc((void **)&m->d_bodies, (size_t)nsys * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void **)&m->d_rxr, (size_t)nsys * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void **)&m->d_stopped, (size_t)nsys * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void **)&bad, sizeof(h));
+  if (e == hipSuccess)
+    e = hipHostMalloc((void **)&m->h_bodies, (size_t)nsys * sizeof(long long), hipHostMallocDefault);
+  if (e == hipSuccess)
+    e = hipHostMalloc((void **)&m->h_rxr, (size_t)nsys * sizeof(double), hipHostMallocDefault);
+  if (e == hipSuccess)
+    e = hipHostMalloc((void **)&m->h_stopped, (size_t)nsys * sizeof(int), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMemsetAsync(bad, 0, sizeof(h), s);
+  if (e == hipSuccess) {
+    const int64_t items = std::max<int64_t>(n + 1, nnz);
+    const int grid = (int)std::min<int64_t>((items + kBlock - 1) / kBlock, kMaxGrid);
+    hipLaunchKernelGGL(k_many_check, dim3(grid), dim3(kBlock), 0, s, (int)n, (int)nnz, d_rowptr,
+                       d_col, bad);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h, bad, sizeof(h), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (bad) (void)hipFree(bad);
+  if (e != hipSuccess) {
+    many_free(m);
+    if (e == hipErrorOutOfMemory) {
+      set_error("cgx_many_create: out of memory (nsys=%lld)", (long long)nsys);
+      return CGX_ENOMEM;
+    }
+    return hip_fail(e, "cgx_many_create");
+  }
+  if (h[0] || h[1]) {
+    many_free(m);
+    if (h[0])
+      set_error("cgx_many_create: %llu entr%s of rowptr outside a CSR row pointer's (rowptr[0] = "
+                "0, ascending, rowptr[n] = nnz = %lld)", h[0], h[0] == 1 ? "y" : "ies",
+                (long long)nnz);
+    else
+      set_error("cgx_many_create: %llu column ind%s outside [0, %lld)", h[1],
+                h[1] == 1 ? "ex" : "ices", (long long)n);
+    return CGX_EINVAL;
+  }
+  *out = m;
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_destroy(cgx_many *m) {
+  if (!m) return CGX_OK;
+  DeviceGuard g(m->ctx->device);
+  (void)hipStreamSynchronize(m->ctx->stream);
+  many_free(m);
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_config(cgx_many *m, int max_workgroups) {
+  CGX_REQUIRE(m, CGX_EINVAL, "NULL argument");
+  CGX_REQUIRE(max_workgroups >= 0, CGX_EINVAL,
+              "cgx_many_config: max_workgroups %d must not be negative (0: the default, the "
+              "resident workgroups)", max_workgroups);
+  m->max_workgroups = max_workgroups;
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_solve(cgx_many *m, const void *d_B, int64_t ldb, void *d_X, int64_t ldx,
+                              double tol, int64_t max_bodies, int64_t *bodies_out,
+                              double *rxr_out, int *stopped_out) {
+  CGX_REQUIRE(m, CGX_EINVAL, "NULL argument");
+  CGX_REQUIRE(d_B, CGX_EINVAL, "cgx_many_solve: B is NULL");
+  CGX_REQUIRE(d_X, CGX_EINVAL, "cgx_many_solve: X is NULL");
+  CGX_REQUIRE(bodies_out && rxr_out, CGX_EINVAL, "cgx_many_solve: bodies_out or rxr_out is NULL");
+  CGX_REQUIRE(ldb >= m->n && ldx >= m->n, CGX_EINVAL,
+              "cgx_many_solve: ldb %lld or ldx %lld is below n %lld", (long long)ldb,
+              (long long)ldx, (long long)m->n);
+  CGX_REQUIRE((((uintptr_t)d_B | (uintptr_t)d_X) & 7) == 0, CGX_EINVAL,
+              "cgx_many_solve: B and X must be 8-byte aligned");
+  DeviceGuard g(m->ctx->device);
+  hipStream_t s = m->ctx->stream;
+  const int64_t n = m->n;
+  const int64_t cap = max_bodies < 0 ? n + 1 : std::min<int64_t>(n + 1, std::max<int64_t>(max_bodies, 1));
+  ManyArgs a;
+  a.rowptr = m->rowptr;
+  a.col = m->col;
+  a.val = m->val;
+  a.B = (const double *)d_B;
+  a.X = (double *)d_X;
+  a.ldv = m->ldv;
+  a.ldb = ldb;
+  a.ldx = ldx;
+  a.bodies = m->d_bodies;
+  a.rxr = m->d_rxr;
+  a.stopped = m->d_stopped;
+  a.tol = tol;
+  a.nsys = (int)m->nsys;
+  a.n = (int)n;
+  a.cap = (int)cap;
+  const dim3 grid(many_grid(m)), block(kBlock);
+  switch (m->r) {
+    case 1: hipLaunchKernelGGL(k_many_cg<1>, grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(k_many_cg<2>, grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL(k_many_cg<4>, grid, block, 0, s, a); break;
+    case 8: hipLaunchKernelGGL(k_many_cg<8>, grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL(k_many_cg<16>, grid, block, 0, s, a); break;
+  }
+  CGX_HIP(hipGetLastError());
+  const size_t ns = (size_t)m->nsys;
+  CGX_HIP(hipMemcpyAsync(m->h_bodies, m->d_bodies, ns * sizeof(long long), hipMemcpyDeviceToHost, s));
+  CGX_HIP(hipMemcpyAsync(m->h_rxr, m->d_rxr, ns * sizeof(double), hipMemcpyDeviceToHost, s));
+  CGX_HIP(hipMemcpyAsync(m->h_stopped, m->d_stopped, ns * sizeof(int), hipMemcpyDeviceToHost, s));
+  CGX_HIP(hipStreamSynchronize(s));
+  for (size_t i = 0; i < ns; ++i) {
+    bodies_out[i] = (int64_t)m->h_bodies[i];
+    rxr_out[i] = m->h_rxr[i];
+    if (stopped_out) stopped_out[i] = m->h_stopped[i];
+  }
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_info(cgx_many *m, int *workgroups, int *rows_per_thread,
+                             int64_t *lds_bytes) {
+  CGX_REQUIRE(m, CGX_EINVAL, "NULL argument");
+  DeviceGuard g(m->ctx->device);
+  if (workgroups) *workgroups = many_grid(m);
+  if (rows_per_thread) *rows_per_thread = m->r;
+  if (lds_bytes) *lds_bytes = ((int64_t)m->r * kBlock + 16) * (int64_t)sizeof(double);
+  return CGX_OK;
+}

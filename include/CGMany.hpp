@@ -1,0 +1,127 @@
+/*
+ * CGMany.hpp — many small SPD systems on one sparsity pattern, each solved by
+ * one workgroup that runs the whole CG loop (cgx.h "cgx_many").
+ *
+ * An extension: the reference solves one system. A thin C++ layer over the C
+ * ABI in the style of the drop-in CG.hpp; double only (CGMany<float> does not
+ * compile). Every system's result is the single solve's in mode 1, bit for
+ * bit (cgx.h).
+ */
+#ifndef CGSOLVER_CGMANY_HPP
+#define CGSOLVER_CGMANY_HPP
+
+#include <cstdint>
+#include <memory>
+#include <stdexcept>
+#include <type_traits>
+#include <vector>
+
+#include "LinearAlgebraTypes.hpp"
+
+namespace CGSolver {
+
+namespace detail {
+struct ManyDeleter {
+  void operator()(cgx_many *m) const {
+    if (m) cgx_many_destroy(m);
+  }
+};
+}  // namespace detail
+
+template <typename DT> class CGMany {
+  static_assert(std::is_same<DT, double>::value, "CGMany solves double systems");
+
+ public:
+  /**
+   * rows (n + 1) and columns (nnz): the shared CSR pattern; values: nsys * nnz,
+   * system s at values[s * nnz ...]. 1 <= n <= 4096.
+   * @throw std::invalid_argument for sizes that do not fit
+   */
+  CGMany(acpp::sycl::queue &queue, const std::vector<int> &rows, const std::vector<int> &columns,
+         const std::vector<DT> &values)
+      : _queue(queue) {
+    if (rows.size() < 2) throw std::invalid_argument("CGMany: rows needs n + 1 >= 2 entries");
+    _n = (int64_t)rows.size() - 1;
+    _nnz = (int64_t)columns.size();
+    if (_nnz == 0 || values.size() % columns.size() != 0 || values.empty())
+      throw std::invalid_argument("CGMany: values must hold nsys * nnz entries");
+    _nsys = (int64_t)(values.size() / columns.size());
+    _rows = alloc(rows.size() * sizeof(int));
+    _cols = alloc(columns.size() * sizeof(int));
+    _vals = alloc(values.size() * sizeof(DT));
+    check(cgx_h2d(_queue.native(), _rows.get(), rows.data(), rows.size() * sizeof(int)), "CGMany");
+    check(cgx_h2d(_queue.native(), _cols.get(), columns.data(), columns.size() * sizeof(int)),
+          "CGMany");
+    check(cgx_h2d(_queue.native(), _vals.get(), values.data(), values.size() * sizeof(DT)),
+          "CGMany");
+    cgx_many *m = nullptr;
+    check(cgx_many_create(_queue.native(), CGX_F64, _nsys, _n, _nnz, (const int32_t *)_rows.get(),
+                          (const int32_t *)_cols.get(), _vals.get(), _nnz, &m),
+          "cgx_many_create");
+    _many = std::shared_ptr<cgx_many>(m, detail::ManyDeleter());
+  }
+
+  int64_t systems() const { return _nsys; }
+  int64_t dimension() const { return _n; }
+
+  /** cap the grid (0: the resident workgroups); a tuning knob */
+  void setMaxWorkgroups(int g) { check(cgx_many_config(_many.get(), g), "cgx_many_config"); }
+  /** cap the bodies of each solve (-1: n + 1) */
+  void setMaxIterations(long long m) { _max_iterations = m; }
+
+  /** overwrite every system's values in place; the next solve reads them */
+  void setValues(const std::vector<DT> &values) {
+    if ((int64_t)values.size() != _nsys * _nnz)
+      throw std::invalid_argument("CGMany::setValues: values must hold nsys * nnz entries");
+    check(cgx_h2d(_queue.native(), _vals.get(), values.data(), values.size() * sizeof(DT)),
+          "setValues");
+  }
+
+  /**
+   * B and X: nsys * n host values, system-major; X holds the initial guesses
+   * and receives the results. improvement: the absolute tolerance on sqrt(r.r).
+   * @throw std::invalid_argument for a wrong length
+   */
+  void solve(const std::vector<DT> &B, std::vector<DT> &X, DT improvement = static_cast<DT>(0)) {
+    const size_t len = (size_t)(_nsys * _n);
+    if (B.size() != len || X.size() != len)
+      throw std::invalid_argument("CGMany::solve: B and X must hold nsys * n entries");
+    auto dB = alloc(len * sizeof(DT)), dX = alloc(len * sizeof(DT));
+    check(cgx_h2d(_queue.native(), dB.get(), B.data(), len * sizeof(DT)), "solve");
+    check(cgx_h2d(_queue.native(), dX.get(), X.data(), len * sizeof(DT)), "solve");
+    _iterations.assign((size_t)_nsys, 0);
+    _final_rxr.assign((size_t)_nsys, 0.0);
+    _stopped.assign((size_t)_nsys, 0);
+    check(cgx_many_solve(_many.get(), dB.get(), _n, dX.get(), _n, (double)improvement,
+                         _max_iterations, _iterations.data(), _final_rxr.data(), _stopped.data()),
+          "cgx_many_solve");
+    check(cgx_d2h(_queue.native(), X.data(), dX.get(), len * sizeof(DT)), "solve");
+  }
+
+  /** per system: loop bodies, r.r after the last body, stop code (1 rule or NaN, 2 cap) */
+  const std::vector<int64_t> &iterations() const { return _iterations; }
+  const std::vector<double> &finalResidualSquared() const { return _final_rxr; }
+  const std::vector<int> &stopped() const { return _stopped; }
+  cgx_many *handle() const { return _many.get(); }
+
+ private:
+  static void check(int rc, const char *what) { acpp::sycl::detail::check(rc, what); }
+  std::shared_ptr<void> alloc(size_t bytes) {
+    void *p = nullptr;
+    check(cgx_alloc(_queue.native(), bytes, &p), "cgx_alloc");
+    cgx_ctx *ctx = _queue.native();
+    return std::shared_ptr<void>(p, [ctx](void *q) { cgx_free(ctx, q); });
+  }
+
+  acpp::sycl::queue _queue;
+  int64_t _nsys = 0, _n = 0, _nnz = 0;
+  long long _max_iterations = -1;
+  std::shared_ptr<void> _rows, _cols, _vals;
+  std::shared_ptr<cgx_many> _many;
+  std::vector<int64_t> _iterations;
+  std::vector<double> _final_rxr;
+  std::vector<int> _stopped;
+};
+
+}  // namespace CGSolver
+#endif /* CGSOLVER_CGMANY_HPP */

@@ -489,6 +489,69 @@ int cgx_mixed_inner(cgx_mixed *m, cgx_csr **A32, cgx_cg **cg32);
  * its allocated size, as of the call. Replaces nothing in the reference. */
 int cgx_mixed_bytes(cgx_mixed *m, int64_t *bytes);
 
+/* ---- cgx_many: many small systems, one workgroup per system (replaces
+ * nothing in the reference, which solves one system) ----------
+ * nsys SPD systems of n <= 4,096 rows share one sparsity pattern (d_rowptr:
+ * n + 1 entries, d_col: nnz entries, entries in CSR order as given); system s
+ * has its own values at d_val + s * ldv, its right-hand side at d_B + s * ldb
+ * and its initial guess / result at d_X + s * ldx. One workgroup of 256
+ * threads runs a whole solve (init and every body; p in LDS, the own rows' x
+ * and r in registers, a dot a workgroup reduction), then takes the next
+ * system: no kernel boundary, no graph replay, no exchange between workgroups.
+ * Arithmetic (normative): system s's x, body count, stop code and final r.r
+ * equal, bit for bit, those of cgx_cg_solve in mode 1 on a cgx_csr made from
+ * (rowptr, col, val_s) with the same b_s, x0_s, tol and cap, wherever both
+ * dots of that run are clear of a rounding boundary (cgx_dd.h): the single
+ * kernels' per-element expressions, products rounded before adds, a row summed
+ * by one thread from 0 in ascending entry order whatever its length (the
+ * single solve tree-sums a row longer than a tile), double-length dots rounded
+ * once, alpha = rr / pAp, beta = rr' / rr, stop rule Q5 (the r.r a body began
+ * with, tested after that body's x update; NaN stops). A NaN or Inf in one
+ * system's values, b or x0 stops that system and reaches no other.
+ * Measured with tools/many_bench.py on an MI355X (4,096 systems to 1e-8 ||b||,
+ * three interleaved rounds, medians; profiles/many_bench.log), µs per system:
+ * scaled 32 x 32 Poisson 3.85 against 1,998 for a cgx_cg_solve per system
+ * (auto mode 5, create not counted) and 19.2 for one solve on the block-diagonal
+ * assembly; irregular_spd(1000) 6.36 against 2,974 and 37.9.
+ * Out of scope: f32 systems, a preconditioner, a wave-per-system form for
+ * n <= 64, systems with differing patterns, partitioned or multi-GPU use, and
+ * any auto route from cgx_cg_solve into this path. */
+typedef struct cgx_many cgx_many;
+/* dtype: CGX_F64 (CGX_F32: CGX_EUNSUPPORTED). 1 <= n <= 4,096 (above:
+ * CGX_EUNSUPPORTED; use cgx_cg_solve), nsys >= 1, ldv >= nnz, rows of any
+ * length, an empty row included. The arrays are the caller's and stay alive
+ * until cgx_many_destroy. The VALUES are read at every solve: a caller may
+ * overwrite them in place between solves, which is how a time-stepping caller
+ * refreshes its matrices without a new create; values in [nnz, ldv) are never
+ * read. The pattern is checked once, here, on the device: CGX_EINVAL for
+ * rowptr[0] != 0, rowptr[n] != nnz, a descending rowptr or a column outside
+ * [0, n); also for nsys < 1, ldv < nnz, a NULL pointer, values that are not
+ * 8-byte aligned. Blocking. Replaces nothing in the reference. */
+int cgx_many_create(cgx_ctx *ctx, int dtype, int64_t nsys, int64_t n, int64_t nnz,
+                    const int32_t *d_rowptr, const int32_t *d_col, const void *d_val,
+                    int64_t ldv, cgx_many **out);
+/* Replaces nothing in the reference. */
+int cgx_many_destroy(cgx_many *m);
+/* max_workgroups caps the grid, min(nsys, resident workgroups,
+ * max_workgroups); 0: no cap (the default), negative: CGX_EINVAL. A tuning
+ * knob, as cgx_cg_config: a workgroup takes systems blockIdx, blockIdx + grid,
+ * ... and the results do not depend on it. Replaces nothing in the reference. */
+int cgx_many_config(cgx_many *m, int max_workgroups);
+/* Blocking. d_B, d_X: system-major f64 device arrays, 8-byte aligned, ldb and
+ * ldx >= n (CGX_EINVAL otherwise); elements in [n, ld) are neither read nor
+ * written. tol is absolute on sqrt(r.r); the cap is min(n + 1, max_bodies), or
+ * n + 1 when max_bodies < 0: both as cgx_cg_solve's. Host outputs of nsys
+ * entries: bodies_out, rxr_out (the r.r after each system's last body),
+ * stopped_out (may be NULL; cgx_cg_solve_batch's codes: 1 stop rule or NaN,
+ * 2 cap reached). Replaces nothing in the reference. */
+int cgx_many_solve(cgx_many *m, const void *d_B, int64_t ldb, void *d_X, int64_t ldx, double tol,
+                   int64_t max_bodies, int64_t *bodies_out, double *rxr_out, int *stopped_out);
+/* *workgroups: the grid the next solve launches; *rows_per_thread: the
+ * instantiation (1, 2, 4, 8 or 16: the least with n <= 256 rows_per_thread);
+ * *lds_bytes: its LDS per workgroup. Each may be NULL.
+ * Replaces nothing in the reference. */
+int cgx_many_info(cgx_many *m, int *workgroups, int *rows_per_thread, int64_t *lds_bytes);
+
 /* CG::accuracy (CG.hpp:463-515): blocking; |sum (b-Ax)^2 / sum x^2|. */
 int cgx_accuracy(cgx_ctx *ctx, cgx_csr *A, const void *d_b, const void *d_x,
                  double *out);
