@@ -135,6 +135,9 @@ _SIGS = {
     "cgx_many_solve": (_i32, [_vp, _vp, _i64, _vp, _i64, _dbl, _i64, C.POINTER(_i64),
                               C.POINTER(_dbl), C.POINTER(_i32)]),
     "cgx_many_info": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)]),
+    "cgx_many_set_precond": (_i32, [_vp, _i32, _vp, _i64]),
+    "cgx_many_get_precond": (_i32, [_vp, C.POINTER(_i32)]),
+    "cgx_many_rz": (_i32, [_vp, C.POINTER(_dbl)]),
     "cgx_accuracy": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_dbl)]),
     "cgx_poisson_nnz": (_i64, [_i32, _i32, _i32, _i32, _i64, _i64]),
     "cgx_poisson_fill": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),

@@ -690,7 +690,9 @@ class ManyCG:
     result is the single solve's in mode 1, bit for bit (cgx.h). ValueError /
     TypeError, before any device call, for a float32 ``vals``, a shape that
     does not fit, n outside 1..4096 or a malformed ``rows``. ``set_values``
-    overwrites the values in place for the next solve (no new create)."""
+    overwrites the values in place for the next solve (no new create).
+    ``set_preconditioner`` turns on Jacobi or a caller's diagonal inside the
+    kernel (cgx_many_set_precond); ``rz`` then holds each system's final r.z."""
 
     MAX_N = 4096
 
@@ -717,8 +719,9 @@ class ManyCG:
             raise ValueError(f"max_workgroups {max_workgroups!r} must not be negative")
         self._queue = queue
         self.nsys, self.n, self.nnz = nsys, n, nnz
-        self.bodies = self.rxr = self.stopped = None
+        self.bodies = self.rxr = self.stopped = self.rz = None
         self._h = None
+        self._precond, self._diag = Preconditioner.None_, None
         self._rows = DeviceArray(queue, n + 1, np.int32).upload(rows)
         self._cols = DeviceArray(queue, nnz, np.int32).upload(cols)
         self._vals = DeviceArray(queue, nsys * nnz, np.float64).upload(
@@ -747,13 +750,39 @@ class ManyCG:
             raise ValueError(f"vals has shape {vals.shape}, expected {(self.nsys, self.nnz)}")
         self._vals.upload(vals.ravel())
 
+    def set_preconditioner(self, kind, diag=None) -> None:
+        """The next solves' preconditioner: ``Preconditioner.None_``, ``Jacobi``
+        (1 / a_ii, formed in the kernel from the values each solve reads) or
+        ``Diagonal`` with ``diag`` (nsys, n), system s's m in row s. A system
+        whose diagonal (Jacobi) or m (Diagonal) is not positive and finite
+        stops alone with code 3 and its x untouched. ValueError, before any
+        device call, for an unknown kind, a missing ``diag`` or a wrong shape."""
+        try:
+            kind = Preconditioner(kind)
+        except ValueError:
+            raise ValueError(f"unknown preconditioner kind {kind!r}") from None
+        d_diag = None
+        if kind == Preconditioner.Diagonal:
+            if diag is None:
+                raise ValueError("Preconditioner.Diagonal needs diag, an (nsys, n) array")
+            diag = np.asarray(diag, dtype=np.float64)
+            if diag.shape != (self.nsys, self.n):
+                raise ValueError(f"diag has shape {diag.shape}, expected {(self.nsys, self.n)}")
+            d_diag = DeviceArray(self._queue, self.nsys * self.n, np.float64).upload(diag.ravel())
+        check(lib().cgx_many_set_precond(self._h, int(kind), d_diag.ptr if d_diag else None,
+                                         self.n))
+        self._precond, self._diag = kind, d_diag  # (the old diag lives until the call above)
+        self.rz = None
+
     def solve(self, B, X0=None, improvement: float = 0.0, max_iter: int = -1) -> np.ndarray:
         """Solve A_s x_s = b_s for every s: ``B`` (nsys, n), ``X0`` the initial
         guesses (same shape; default 0). ``improvement`` is the absolute
         tolerance on sqrt(r.r) and ``max_iter`` caps the bodies (-1: n + 1), as
         CG.solve's. Returns X (nsys, n) and sets ``bodies``, ``rxr`` (the r.r
-        after each system's last body) and ``stopped`` (1 stop rule or NaN,
-        2 cap). ValueError, before any device call, for a wrong shape."""
+        after each system's last body), ``stopped`` (1 stop rule or NaN,
+        2 cap, 3 a bad diagonal under a preconditioner) and, under a
+        preconditioner, ``rz`` (else None). ValueError, before any device
+        call, for a wrong shape."""
         B = np.asarray(B)
         if B.shape != (self.nsys, self.n):
             raise ValueError(f"B has shape {B.shape}, expected {(self.nsys, self.n)}")
@@ -775,6 +804,11 @@ class ManyCG:
         self.bodies = np.array(bodies[:], dtype=np.int64)
         self.rxr = np.array(rxr[:], dtype=np.float64)
         self.stopped = np.array(stopped[:], dtype=np.int32)
+        self.rz = None
+        if getattr(self, "_precond", Preconditioner.None_) != Preconditioner.None_:
+            rz = (C.c_double * ns)()
+            check(lib().cgx_many_rz(self._h, rz))
+            self.rz = np.array(rz[:], dtype=np.float64)
         return dX.download().reshape(ns, n)
 
     def close(self) -> None:

@@ -11,9 +11,12 @@
 // bit: the single kernels' per-element expressions with products rounded
 // before adds (-ffp-contract=off), a row summed by one thread from 0 in
 // ascending entry order, the dots double-length sums (cgx_dd.h) rounded once,
-// stop rule Q5 as k_update_xp applies it.
+// stop rule Q5 as k_update_xp applies it. With cgx_many_set_precond the same
+// kernel runs PCG with a diagonal M^-1 (k_many_cg's PC), pinned the same way
+// to mode 1 under cgx_cg_set_precond.
 #include <cmath>
 #include <climits>
+#include <limits>
 #include <map>
 #include <mutex>
 
@@ -40,7 +43,16 @@ struct ManyArgs {
   int *stopped;
   double tol;
   int nsys, n, cap;
+  // the preconditioned form's (last: the plain form's arguments stay where they were)
+  const double *M;  // DIAGONAL: the caller's m, system s at M + s ldm; JACOBI: NULL
+  int64_t ldm;
+  double *rz;       // per system: r.z after the last body
 };
+
+// k_diag_inv's verdict on a diagonal (or on a caller's m): positive and finite
+__device__ __forceinline__ bool many_pc_ok(double d) {
+  return d > 0.0 && d <= std::numeric_limits<double>::max();  // false for NaN
+}
 
 // The workgroup sum of one pair per thread, rounded once, in every thread:
 // waves first (wave_sum_dd), then wave 0 to 3 in that order, as
@@ -60,13 +72,62 @@ __device__ __forceinline__ double many_sum(Dd<double> v, double *red) {
   return s.value();
 }
 
+// Two workgroup sums behind one barrier: many_sum's value for each pair (the
+// same wave sums, the same wave order). red: 16 doubles, as many_sum's 8.
+__device__ __forceinline__ void many_sum2(Dd<double> u, Dd<double> v, double *red, double *su,
+                                          double *sv) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  u = wave_sum_dd(u);
+  v = wave_sum_dd(v);
+  if (lane == 0) {
+    red[2 * w] = u.hi;
+    red[2 * w + 1] = u.lo;
+    red[8 + 2 * w] = v.hi;
+    red[8 + 2 * w + 1] = v.lo;
+  }
+  __syncthreads();
+  Dd<double> s(red[0], red[1]), z(red[8], red[9]);
+#pragma unroll
+  for (int k = 1; k < kBlock / 64; ++k) {
+    s += Dd<double>(red[2 * k], red[2 * k + 1]);
+    z += Dd<double>(red[8 + 2 * k], red[8 + 2 * k + 1]);
+  }
+  *su = s.value();
+  *sv = z.value();
+}
+
 // R rows per thread: n <= R kBlock. LDS: p (R kBlock doubles) and two
 // reduction stagings.
-template <int R>
+//
+// PC: diagonal preconditioning (cgx_many_set_precond), statement for statement
+// as k_pc_init, update_r_pc_body, k_update_xp_pc and pc_stop_rule
+// (cgx_kernels.hip): z_i = m_i * r_i, rounded, never stored beyond the body
+// that forms it (it takes Ap's register once r is updated); alpha = rz / p.Ap,
+// beta = rz' / rz, r.r and r.z summed behind one barrier, so a body keeps its
+// three barriers; the stop rule tests the true r.r. m is a second R kBlock
+// doubles of LDS that a thread reads and writes only at its own rows (stride
+// 1, no barrier of its own): a.M's entries (DIAGONAL), or 1 / a_ii formed by
+// the row's thread from the values this solve reads (JACOBI, a.M == NULL; the
+// entries with col == row summed from 0 in entry order, as k_diag_inv), so a
+// caller who overwrites the values in place never meets a stale diagonal.
+// A row without a diagonal entry (JACOBI), or a d (JACOBI) or m_i (DIAGONAL)
+// that is not positive and finite, ends that system before anything of it is
+// written: X as given, 0 bodies, NaN r.r and r.z, stop code 3. `refused`
+// carries the verdict across the init's first barrier; the extra barrier of
+// that path keeps a thread that is already at the next system from writing
+// the word while another still reads it. The plain form (PC = false) is the
+// code it was: every addition is behind `if constexpr (PC)`.
+template <int R, bool PC>
 __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
   __shared__ double p[R * kBlock];
-  __shared__ double red[2][8];
+  __shared__ double red[2][PC ? 16 : 8];
+  __shared__ double mm[PC ? R * kBlock : 1];  // (unused, and dropped, without PC)
+  __shared__ int refused;                     // (the same)
   const int t = threadIdx.x, n = a.n;
+  if constexpr (PC) {
+    if (t == 0) refused = 0;
+    __syncthreads();
+  }
   // the pattern is every system's: a thread's row bounds stay in registers
   int e0[R], e1[R];
 #pragma unroll
@@ -87,7 +148,45 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
       x[k] = i < n ? xs[i] : 0.0;
       if (i < n) p[i] = x[k];  // x through LDS: the init's gather source
     }
+    if constexpr (PC) {  // m of the own rows, and the verdict on it
+      bool bad = false;
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = t + k * kBlock;
+        if (i < n) {
+          double mv;
+          if (a.M) {
+            mv = a.M[(int64_t)s * a.ldm + i];
+            bad = bad || !many_pc_ok(mv);
+          } else {
+            double d = 0.0;
+            bool found = false;
+            for (int e = e0[k]; e < e1[k]; ++e)
+              if (a.col[e] == i) {
+                d = d + val[e];
+                found = true;
+              }
+            mv = 1.0 / d;
+            bad = bad || !found || !many_pc_ok(d);
+          }
+          mm[i] = mv;
+        }
+      }
+      if (bad) refused = s + 1;  // (s + 1 > 0 marks this system alone: no reset)
+    }
     __syncthreads();
+    if constexpr (PC) {
+      if (refused == s + 1) {  // uniform: every thread reads it behind the barrier
+        if (t == 0) {
+          a.bodies[s] = 0;
+          a.rxr[s] = __builtin_nan("");
+          a.rz[s] = __builtin_nan("");
+          a.stopped[s] = 3;
+        }
+        __syncthreads();  // every read of `refused`, before the next system may write it
+        continue;
+      }
+    }
     Dd<double> acc(0.0);
 #pragma unroll
     for (int k = 0; k < R; ++k) {
@@ -101,12 +200,27 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
       }
     }
     __syncthreads();  // every gather of x is done: p may be overwritten
+    double rxr, rz = 0.0;
+    if constexpr (PC) {  // p = m o r, rz = r.(m o r) (k_pc_init)
+      Dd<double> accz(0.0);
 #pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int i = t + k * kBlock;
-      if (i < n) p[i] = r[k];
+      for (int k = 0; k < R; ++k) {
+        const int i = t + k * kBlock;
+        if (i < n) {
+          const double z = mm[i] * r[k];
+          p[i] = z;
+          accz += r[k] * z;
+        }
+      }
+      many_sum2(acc, accz, red[1], &rxr, &rz);  // (its barrier publishes p too)
+    } else {
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = t + k * kBlock;
+        if (i < n) p[i] = r[k];
+      }
+      rxr = many_sum(acc, red[1]);  // (its barrier publishes p too)
     }
-    double rxr = many_sum(acc, red[1]);  // (its barrier publishes p too)
     long long bodies = 0;
     int stopped = 0;
     // ---- the bodies ----
@@ -123,28 +237,47 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
         if (i < n) acc += sum * p[i];
       }
       const double pAp = many_sum(acc, red[0]);
-      const double alpha = rxr / pAp;
-      // r -= alpha Ap and r.r (k_update_r)
+      const double alpha = (PC ? rz : rxr) / pAp;
+      // r -= alpha Ap and r.r (k_update_r); PC: r.z in the same sweep, z
+      // kept where Ap was (update_r_pc_body)
       acc = Dd<double>(0.0);
+      double rr, rzn = 0.0;
+      if constexpr (PC) {
+        Dd<double> accz(0.0);
 #pragma unroll
-      for (int k = 0; k < R; ++k) {
-        const int i = t + k * kBlock;
-        if (i < n) {
-          r[k] = r[k] - alpha * Ap[k];
-          acc += r[k] * r[k];
+        for (int k = 0; k < R; ++k) {
+          const int i = t + k * kBlock;
+          if (i < n) {
+            r[k] = r[k] - alpha * Ap[k];
+            acc += r[k] * r[k];
+            const double z = mm[i] * r[k];
+            accz += r[k] * z;
+            Ap[k] = z;
+          }
         }
+        many_sum2(acc, accz, red[1], &rr, &rzn);
+      } else {
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+          const int i = t + k * kBlock;
+          if (i < n) {
+            r[k] = r[k] - alpha * Ap[k];
+            acc += r[k] * r[k];
+          }
+        }
+        rr = many_sum(acc, red[1]);
       }
-      const double rr = many_sum(acc, red[1]);
-      const double beta = rr / rxr;
-      // x += alpha p; p = r + beta p; the stop rule (k_update_xp). Every
-      // gather of this body's p lies before the two barriers above.
+      const double beta = PC ? rzn / rz : rr / rxr;
+      // x += alpha p; p = r + beta p (PC: m o r + beta p); the stop rule
+      // (k_update_xp, k_update_xp_pc). Every gather of this body's p lies
+      // before the two barriers above.
 #pragma unroll
       for (int k = 0; k < R; ++k) {
         const int i = t + k * kBlock;
         if (i < n) {
           const double pv = p[i];
           x[k] = x[k] + alpha * pv;
-          p[i] = r[k] + beta * pv;
+          p[i] = (PC ? Ap[k] : r[k]) + beta * pv;
         }
       }
       ++bodies;
@@ -152,6 +285,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
       const bool cont = !cond && bodies < a.cap;
       stopped = cond ? 1 : (cont ? 0 : 2);
       rxr = rr;
+      if constexpr (PC) rz = rzn;
       __syncthreads();  // the new p, before the next gather (or the next system's x)
       if (!cont) break;
     }
@@ -164,6 +298,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
       a.bodies[s] = bodies;
       a.rxr[s] = rxr;
       a.stopped[s] = stopped;
+      if constexpr (PC) a.rz[s] = rz;
     }
   }
 }
@@ -198,32 +333,38 @@ int many_rows_per_thread(int64_t n) {
   return r;
 }
 
-const void *many_kernel(int r) {
+template <bool PC> const void *many_kernel_of(int r) {
   switch (r) {
-    case 1: return reinterpret_cast<const void *>(&k_many_cg<1>);
-    case 2: return reinterpret_cast<const void *>(&k_many_cg<2>);
-    case 4: return reinterpret_cast<const void *>(&k_many_cg<4>);
-    case 8: return reinterpret_cast<const void *>(&k_many_cg<8>);
-    case 16: return reinterpret_cast<const void *>(&k_many_cg<16>);
+    case 1: return reinterpret_cast<const void *>(&k_many_cg<1, PC>);
+    case 2: return reinterpret_cast<const void *>(&k_many_cg<2, PC>);
+    case 4: return reinterpret_cast<const void *>(&k_many_cg<4, PC>);
+    case 8: return reinterpret_cast<const void *>(&k_many_cg<8, PC>);
+    case 16: return reinterpret_cast<const void *>(&k_many_cg<16, PC>);
     default: return nullptr;
   }
 }
 
-// workgroups of k_many_cg<r> resident on the device at once (occupancy x
+const void *many_kernel(int r, bool pc) {
+  return pc ? many_kernel_of<true>(r) : many_kernel_of<false>(r);
+}
+
+// workgroups of k_many_cg<r, pc> resident on the device at once (occupancy x
 // CUs; 0: unknown), as spmv_dot_resident
-int many_resident(int r) {
+int many_resident(int r, bool pc) {
   static std::mutex mu;
-  static std::map<std::pair<int, int>, int> cache;  // (device, r) -> workgroups
+  static std::map<std::pair<int, int>, int> cache;  // (device, r or -r with pc) -> workgroups
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find({dev, r});
+  const std::pair<int, int> key{dev, pc ? -r : r};
+  auto it = cache.find(key);
   if (it != cache.end()) return it->second;
   int res = 0, nb = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, many_kernel(r), kBlock, 0) == hipSuccess &&
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, many_kernel(r, pc), kBlock, 0) ==
+          hipSuccess &&
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
     res = nb * cus;
-  cache[{dev, r}] = res;
+  cache[key] = res;
   return res;
 }
 
@@ -236,11 +377,15 @@ struct cgx_many {
   const double *val = nullptr;
   int r = 1;               // rows per thread
   int max_workgroups = 0;  // cgx_many_config (0: the resident workgroups)
+  int precond = CGX_PRECOND_NONE;  // cgx_many_set_precond: the next solve's
+  const double *d_M = nullptr;     // DIAGONAL: the caller's
+  int64_t ldm = 0;
+  bool rz_valid = false;  // the last solve was preconditioned, with this preconditioner
   long long *d_bodies = nullptr;
-  double *d_rxr = nullptr;
+  double *d_rxr = nullptr, *d_rz = nullptr;
   int *d_stopped = nullptr;
   long long *h_bodies = nullptr;  // pinned, nsys each
-  double *h_rxr = nullptr;
+  double *h_rxr = nullptr, *h_rz = nullptr;
   int *h_stopped = nullptr;
 };
 
@@ -248,19 +393,30 @@ namespace {
 
 void many_free(cgx_many *m) {
   if (!m) return;
-  void *dev[] = {m->d_bodies, m->d_rxr, m->d_stopped};
+  void *dev[] = {m->d_bodies, m->d_rxr, m->d_rz, m->d_stopped};
   for (void *p : dev)
     if (p) (void)hipFree(p);
-  void *host[] = {m->h_bodies, m->h_rxr, m->h_stopped};
+  void *host[] = {m->h_bodies, m->h_rxr, m->h_rz, m->h_stopped};
   for (void *p : host)
     if (p) (void)hipHostFree(p);
   if (m->ctx) ctx_release(m->ctx);
   delete m;
 }
 
+template <bool PC>
+void many_launch(int r, dim3 grid, dim3 block, hipStream_t s, const ManyArgs &a) {
+  switch (r) {
+    case 1: hipLaunchKernelGGL((k_many_cg<1, PC>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((k_many_cg<2, PC>), grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((k_many_cg<4, PC>), grid, block, 0, s, a); break;
+    case 8: hipLaunchKernelGGL((k_many_cg<8, PC>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((k_many_cg<16, PC>), grid, block, 0, s, a); break;
+  }
+}
+
 int many_grid(const cgx_many *m) {
   int64_t g = m->nsys;
-  const int res = many_resident(m->r);
+  const int res = many_resident(m->r, m->precond != CGX_PRECOND_NONE);
   if (res > 0) g = std::min<int64_t>(g, res);
   if (m->max_workgroups > 0) g = std::min<int64_t>(g, m->max_workgroups);
   return (int)std::min<int64_t>(std::max<int64_t>(g, 1), INT_MAX);
@@ -312,12 +468,15 @@ extern "C" int cgx_many_create(cgx_ctx *ctx, int dtype, int64_t nsys, int64_t n,
   unsigned long long *bad = nullptr, h[2] = {0, 0};
   hipError_t e = hipMalloc((void **)&m->d_bodies, (size_t)nsys * sizeof(long long));
   if (e == hipSuccess) e = hipMalloc((void **)&m->d_rxr, (size_t)nsys * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void **)&m->d_rz, (size_t)nsys * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void **)&m->d_stopped, (size_t)nsys * sizeof(int));
   if (e == hipSuccess) e = hipMalloc((void **)&bad, sizeof(h));
   if (e == hipSuccess)
     e = hipHostMalloc((void **)&m->h_bodies, (size_t)nsys * sizeof(long long), hipHostMallocDefault);
   if (e == hipSuccess)
     e = hipHostMalloc((void **)&m->h_rxr, (size_t)nsys * sizeof(double), hipHostMallocDefault);
+  if (e == hipSuccess)
+    e = hipHostMalloc((void **)&m->h_rz, (size_t)nsys * sizeof(double), hipHostMallocDefault);
   if (e == hipSuccess)
     e = hipHostMalloc((void **)&m->h_stopped, (size_t)nsys * sizeof(int), hipHostMallocDefault);
   if (e == hipSuccess) e = hipMemsetAsync(bad, 0, sizeof(h), s);
@@ -403,16 +562,17 @@ extern "C" int cgx_many_solve(cgx_many *m, const void *d_B, int64_t ldb, void *d
   a.nsys = (int)m->nsys;
   a.n = (int)n;
   a.cap = (int)cap;
+  const bool pc = m->precond != CGX_PRECOND_NONE;
+  a.M = m->precond == CGX_PRECOND_DIAGONAL ? m->d_M : nullptr;
+  a.ldm = m->ldm;
+  a.rz = m->d_rz;
+  m->rz_valid = false;
   const dim3 grid(many_grid(m)), block(kBlock);
-  switch (m->r) {
-    case 1: hipLaunchKernelGGL(k_many_cg<1>, grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL(k_many_cg<2>, grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL(k_many_cg<4>, grid, block, 0, s, a); break;
-    case 8: hipLaunchKernelGGL(k_many_cg<8>, grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL(k_many_cg<16>, grid, block, 0, s, a); break;
-  }
+  if (pc) many_launch<true>(m->r, grid, block, s, a);
+  else many_launch<false>(m->r, grid, block, s, a);
   CGX_HIP(hipGetLastError());
   const size_t ns = (size_t)m->nsys;
+  if (pc) CGX_HIP(hipMemcpyAsync(m->h_rz, m->d_rz, ns * sizeof(double), hipMemcpyDeviceToHost, s));
   CGX_HIP(hipMemcpyAsync(m->h_bodies, m->d_bodies, ns * sizeof(long long), hipMemcpyDeviceToHost, s));
   CGX_HIP(hipMemcpyAsync(m->h_rxr, m->d_rxr, ns * sizeof(double), hipMemcpyDeviceToHost, s));
   CGX_HIP(hipMemcpyAsync(m->h_stopped, m->d_stopped, ns * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -422,6 +582,43 @@ extern "C" int cgx_many_solve(cgx_many *m, const void *d_B, int64_t ldb, void *d
     rxr_out[i] = m->h_rxr[i];
     if (stopped_out) stopped_out[i] = m->h_stopped[i];
   }
+  m->rz_valid = pc;
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_set_precond(cgx_many *m, int kind, const void *d_M, int64_t ldm) {
+  CGX_REQUIRE(kind == CGX_PRECOND_NONE || kind == CGX_PRECOND_JACOBI ||
+                  kind == CGX_PRECOND_DIAGONAL,
+              CGX_EINVAL, "cgx_many_set_precond: unknown kind %d", kind);
+  if (kind == CGX_PRECOND_DIAGONAL) {
+    CGX_REQUIRE(d_M, CGX_EINVAL, "cgx_many_set_precond: DIAGONAL needs d_M, which is NULL");
+    CGX_REQUIRE(((uintptr_t)d_M & 7) == 0, CGX_EINVAL,
+                "cgx_many_set_precond: d_M must be 8-byte aligned");
+  }
+  CGX_REQUIRE(m, CGX_EINVAL, "cgx_many_set_precond: NULL handle");
+  if (kind == CGX_PRECOND_DIAGONAL)
+    CGX_REQUIRE(ldm >= m->n, CGX_EINVAL, "cgx_many_set_precond: ldm %lld is below n %lld",
+                (long long)ldm, (long long)m->n);
+  m->precond = kind;
+  m->d_M = kind == CGX_PRECOND_DIAGONAL ? (const double *)d_M : nullptr;
+  m->ldm = kind == CGX_PRECOND_DIAGONAL ? ldm : 0;
+  m->rz_valid = false;
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_get_precond(cgx_many *m, int *kind) {
+  CGX_REQUIRE(m && kind, CGX_EINVAL, "cgx_many_get_precond: NULL argument");
+  *kind = m->precond;
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_rz(cgx_many *m, double *rz_out) {
+  CGX_REQUIRE(m && rz_out, CGX_EINVAL, "cgx_many_rz: NULL argument");
+  CGX_REQUIRE(m->precond != CGX_PRECOND_NONE, CGX_ESTATE,
+              "cgx_many_rz: no preconditioner is set");
+  CGX_REQUIRE(m->rz_valid, CGX_ESTATE,
+              "cgx_many_rz: no solve has run under this preconditioner");
+  for (int64_t i = 0; i < m->nsys; ++i) rz_out[i] = m->h_rz[i];
   return CGX_OK;
 }
 
@@ -431,6 +628,9 @@ extern "C" int cgx_many_info(cgx_many *m, int *workgroups, int *rows_per_thread,
   DeviceGuard g(m->ctx->device);
   if (workgroups) *workgroups = many_grid(m);
   if (rows_per_thread) *rows_per_thread = m->r;
-  if (lds_bytes) *lds_bytes = ((int64_t)m->r * kBlock + 16) * (int64_t)sizeof(double);
+  if (lds_bytes)  // p and the stagings; preconditioned: m, wider stagings and the verdict word
+    *lds_bytes = m->precond == CGX_PRECOND_NONE
+                     ? ((int64_t)m->r * kBlock + 16) * (int64_t)sizeof(double)
+                     : ((int64_t)2 * m->r * kBlock + 32) * (int64_t)sizeof(double) + 8;
   return CGX_OK;
 }

@@ -5,7 +5,7 @@
  * An extension: the reference solves one system. A thin C++ layer over the C
  * ABI in the style of the drop-in CG.hpp; double only (CGMany<float> does not
  * compile). Every system's result is the single solve's in mode 1, bit for
- * bit (cgx.h).
+ * bit (cgx.h), plain or under setPreconditioner's Jacobi / diagonal.
  */
 #ifndef CGSOLVER_CGMANY_HPP
 #define CGSOLVER_CGMANY_HPP
@@ -78,6 +78,32 @@ template <typename DT> class CGMany {
   }
 
   /**
+   * The next solves' preconditioner (cgx_many_set_precond): kind is
+   * CGX_PRECOND_NONE, CGX_PRECOND_JACOBI (1 / a_ii, formed in the kernel from
+   * the values each solve reads) or CGX_PRECOND_DIAGONAL with *diag, nsys * n
+   * host values, system s's m at diag[s * n ...]. A system whose diagonal or m
+   * is not positive and finite stops alone with code 3, its X untouched.
+   * @throw std::invalid_argument for an unknown kind, a missing diag or a wrong length
+   */
+  void setPreconditioner(int kind, const std::vector<DT> *diag = nullptr) {
+    if (kind != CGX_PRECOND_NONE && kind != CGX_PRECOND_JACOBI && kind != CGX_PRECOND_DIAGONAL)
+      throw std::invalid_argument("CGMany::setPreconditioner: unknown kind");
+    std::shared_ptr<void> d;
+    if (kind == CGX_PRECOND_DIAGONAL) {
+      if (!diag || (int64_t)diag->size() != _nsys * _n)
+        throw std::invalid_argument("CGMany::setPreconditioner: diag must hold nsys * n entries");
+      d = alloc(diag->size() * sizeof(DT));
+      check(cgx_h2d(_queue.native(), d.get(), diag->data(), diag->size() * sizeof(DT)),
+            "setPreconditioner");
+    }
+    check(cgx_many_set_precond(_many.get(), kind, d.get(), _n), "cgx_many_set_precond");
+    _diag = d;
+    _precond = kind;
+    _final_rz.clear();
+  }
+  int preconditioner() const { return _precond; }
+
+  /**
    * B and X: nsys * n host values, system-major; X holds the initial guesses
    * and receives the results. improvement: the absolute tolerance on sqrt(r.r).
    * @throw std::invalid_argument for a wrong length
@@ -95,12 +121,20 @@ template <typename DT> class CGMany {
     check(cgx_many_solve(_many.get(), dB.get(), _n, dX.get(), _n, (double)improvement,
                          _max_iterations, _iterations.data(), _final_rxr.data(), _stopped.data()),
           "cgx_many_solve");
+    _final_rz.clear();
+    if (_precond != CGX_PRECOND_NONE) {
+      _final_rz.assign((size_t)_nsys, 0.0);
+      check(cgx_many_rz(_many.get(), _final_rz.data()), "cgx_many_rz");
+    }
     check(cgx_d2h(_queue.native(), X.data(), dX.get(), len * sizeof(DT)), "solve");
   }
 
-  /** per system: loop bodies, r.r after the last body, stop code (1 rule or NaN, 2 cap) */
+  /** per system: loop bodies, r.r after the last body, stop code (1 rule or NaN, 2 cap,
+   *  3 a bad diagonal under a preconditioner); finalRz: r.z after the last body (empty
+   *  without a preconditioner) */
   const std::vector<int64_t> &iterations() const { return _iterations; }
   const std::vector<double> &finalResidualSquared() const { return _final_rxr; }
+  const std::vector<double> &finalRz() const { return _final_rz; }
   const std::vector<int> &stopped() const { return _stopped; }
   cgx_many *handle() const { return _many.get(); }
 
@@ -116,10 +150,11 @@ template <typename DT> class CGMany {
   acpp::sycl::queue _queue;
   int64_t _nsys = 0, _n = 0, _nnz = 0;
   long long _max_iterations = -1;
-  std::shared_ptr<void> _rows, _cols, _vals;
+  std::shared_ptr<void> _rows, _cols, _vals, _diag;
+  int _precond = CGX_PRECOND_NONE;
   std::shared_ptr<cgx_many> _many;
   std::vector<int64_t> _iterations;
-  std::vector<double> _final_rxr;
+  std::vector<double> _final_rxr, _final_rz;
   std::vector<int> _stopped;
 };
 

@@ -513,9 +513,12 @@ int cgx_mixed_bytes(cgx_mixed *m, int64_t *bytes);
  * scaled 32 x 32 Poisson 3.85 against 1,998 for a cgx_cg_solve per system
  * (auto mode 5, create not counted) and 19.2 for one solve on the block-diagonal
  * assembly; irregular_spd(1000) 6.36 against 2,974 and 37.9.
- * Out of scope: f32 systems, a preconditioner, a wave-per-system form for
- * n <= 64, systems with differing patterns, partitioned or multi-GPU use, and
- * any auto route from cgx_cg_solve into this path. */
+ * Diagonal preconditioning (cgx_many_set_precond) runs in the same kernel: see
+ * there.
+ * Out of scope: f32 systems, a preconditioner other than a diagonal, a
+ * wave-per-system form for n <= 64, systems with differing patterns,
+ * partitioned or multi-GPU use, and any auto route from cgx_cg_solve into this
+ * path. */
 typedef struct cgx_many cgx_many;
 /* dtype: CGX_F64 (CGX_F32: CGX_EUNSUPPORTED). 1 <= n <= 4,096 (above:
  * CGX_EUNSUPPORTED; use cgx_cg_solve), nsys >= 1, ldv >= nnz, rows of any
@@ -551,6 +554,42 @@ int cgx_many_solve(cgx_many *m, const void *d_B, int64_t ldb, void *d_X, int64_t
  * *lds_bytes: its LDS per workgroup. Each may be NULL.
  * Replaces nothing in the reference. */
 int cgx_many_info(cgx_many *m, int *workgroups, int *rows_per_thread, int64_t *lds_bytes);
+/* Diagonal preconditioning inside the many-systems kernel. kind: CGX_PRECOND_NONE
+ * (the default), CGX_PRECOND_JACOBI or CGX_PRECOND_DIAGONAL; it may be set
+ * between solves and takes effect at the next one (cgx_many_info then reports
+ * the preconditioned instantiation's grid and LDS). NONE and JACOBI ignore d_M
+ * and ldm. JACOBI: m_i = 1 / a_ii, a_ii the row's entries with col == row
+ * summed from 0 in entry order, formed in the kernel at EVERY solve from the
+ * values that solve reads, so values overwritten in place never meet a stale
+ * diagonal. DIAGONAL: system s's m is the n f64 values at d_M + s * ldm,
+ * ldm >= n; the array is the caller's, 8-byte aligned, alive until replaced or
+ * cgx_many_destroy, read at every solve; [n, ldm) is never read.
+ * Arithmetic (normative): system s's x, body count, stop code, final r.r and
+ * final r.z equal, bit for bit, those of cgx_cg_solve in mode 1 with
+ * cgx_cg_set_precond(kind) on that system alone, wherever the run's dots are
+ * clear of a rounding boundary: z = m o r rounded and never stored,
+ * alpha = rz / p.Ap, r.r and r.z in one sweep, beta = rz' / rz,
+ * p = m o r + beta p, stop rule Q5 on the true r.r. With m == 1 every value
+ * is the plain kernel's.
+ * A bad diagonal stops its own system and no other: where a row has no
+ * diagonal entry or a_ii is not positive and finite (JACOBI), or an m_i is
+ * not positive and finite (DIAGONAL), that system's X is left exactly as
+ * given and it reports 0 bodies, NaN r.r, NaN r.z and stop code 3; the call
+ * still returns CGX_OK. Code 3 does not occur without a preconditioner.
+ * Measured with tools/many_pcg_bench.py on an MI355X (many_bench's systems,
+ * medians; profiles/many_pcg_bench.log), µs per system plain -> JACOBI: scaled
+ * 32 x 32 Poisson 3.89 -> 0.98 (418 -> 104 bodies), irregular_spd(1000) 6.44 ->
+ * 1.31 (381 -> 73); a preconditioned body costs 1.5 to 6.5 % more.
+ * CGX_EINVAL, before any device call, for a NULL handle, an unknown kind,
+ * DIAGONAL with a NULL or misaligned d_M or ldm < n; on an error the object
+ * keeps the preconditioner it had. Replaces nothing in the reference. */
+int cgx_many_set_precond(cgx_many *m, int kind, const void *d_M, int64_t ldm);
+/* Replaces nothing in the reference. */
+int cgx_many_get_precond(cgx_many *m, int *kind);
+/* nsys host values: r.z after each system's last body in the last solve.
+ * CGX_ESTATE without a preconditioner, or before a solve under the one that
+ * is set. Replaces nothing in the reference. */
+int cgx_many_rz(cgx_many *m, double *rz_out);
 
 /* CG::accuracy (CG.hpp:463-515): blocking; |sum (b-Ax)^2 / sum x^2|. */
 int cgx_accuracy(cgx_ctx *ctx, cgx_csr *A, const void *d_b, const void *d_x,
