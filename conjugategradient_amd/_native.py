@@ -107,6 +107,7 @@ _SIGS = {
                                  C.POINTER(_i32)]),
     "cgx_cg_coop_trace": (_i32, [_vp, C.POINTER(C.c_uint64), _i64]),
     "cgx_cg_get_mode": (_i32, [_vp, C.POINTER(_i32)]),
+    "cgx_cg_sweep_dirs": (_i32, [_vp, _i32, C.POINTER(_i32), _i32, C.POINTER(_i32)]),
     "cgx_csr_fd_grid": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "cgx_csr_diag_inv": (_i32, [_vp, _vp]),
     "cgx_cg_set_precond": (_i32, [_vp, _i32, _vp]),

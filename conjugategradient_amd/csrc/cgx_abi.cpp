@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "cgx_objects.h"
+#include "cgx_sweep.h"
 
 namespace cgx {
 
@@ -327,6 +328,27 @@ static const PeerDev *fused_ar(const cgx_cg *cg) {
   return (cg->A->dist && cg->A->peer.on && !cg->A->peer.one_waiter) ? &cg->A->peer.dev : nullptr;
 }
 
+// The sweep rule of the resolved mode (cgx_sweep.h): the launches per body
+// the rule counts, and how many of a body's launches take a direction (in
+// stream order, k = 0 ..). Three-kernel bodies (modes 1, 3, 6, preconditioned
+// or partitioned): 3 and 3. The two-kernel bodies on one device (modes 4 and
+// 7): 2 and 2. Mode 4 on a partitioned matrix: the three-kernel rule's first
+// two (interior walk and update_r; the boundary rows have no direction).
+// Modes 2 and 5 sweep forward only: no directed launch.
+struct SweepRule {
+  int per_body, directed;
+};
+static SweepRule sweep_rule(const cgx_cg *cg) {
+  if (cg->coop || cg->fused) return {0, 0};
+  if (cg->fdefer) return cg->A->dist ? SweepRule{3, 2} : SweepRule{2, 2};
+  return {3, 3};
+}
+// direction of the k-th directed launch of the body in `slot` (altdir off:
+// every launch forward)
+static int body_dir(const cgx_cg *cg, int slot, int k) {
+  return cg->altdir ? sweep_dir(sweep_rule(cg).per_body, slot & 3, k) : 0;
+}
+
 template <typename T> int enqueue_iter(cgx_cg *cg, int slot) {
   cgx_csr *A = cg->A;
   hipStream_t s = cg->ctx->stream;
@@ -338,8 +360,9 @@ template <typename T> int enqueue_iter(cgx_cg *cg, int slot) {
   // (single device). A partitioned run finalizes each local dot into the
   // scalar ring, all-reduces it, and the next kernel reads the ring.
   const int npr = Launch<T>::update_parts(cg->n);
-  // sweep directions: each kernel starts where the previous one ended
-  const int par = cg->altdir ? (slot & 1) : 0, rpar = cg->altdir ? 1 - par : 0;
+  // sweep directions: each kernel starts where the previous one ended (body_dir)
+  const int par = body_dir(cg, slot, 0), rpar = body_dir(cg, slot, 1),
+            par3 = body_dir(cg, slot, 2);
   int npp = 0;
   const PeerDev *far = fused_ar(cg);
   const bool sep = A->dist && !far;  // a separate all-reduce step per dot
@@ -355,7 +378,7 @@ template <typename T> int enqueue_iter(cgx_cg *cg, int slot) {
       return rc;
     if (sep && (rc = dist_dot_pair<T>(cg, npr, slot))) return rc;
     return timed(cg, 3, s, [&] {
-      return Launch<T>::update_xp_pc_dist(cg->n, x, p, r, m, st, slot, ws, npr, s, par, far);
+      return Launch<T>::update_xp_pc_dist(cg->n, x, p, r, m, st, slot, ws, npr, s, par3, far);
     });
   }
   if (cg->precond) {  // single device (cgx_cg_set_precond): the SpMV launch is the plain one
@@ -365,7 +388,7 @@ template <typename T> int enqueue_iter(cgx_cg *cg, int slot) {
          })))
       return rc;
     return timed(cg, 3, s, [&] {
-      return Launch<T>::update_xp_pc(cg->n, x, p, r, m, st, slot, ws, npr, s, par, cg->minv_nt);
+      return Launch<T>::update_xp_pc(cg->n, x, p, r, m, st, slot, ws, npr, s, par3, cg->minv_nt);
     });
   }
   if (sep && (rc = dist_dot<T>(cg, ws->pap_part, npp, &st->pAp[slot], slot, 1))) return rc;
@@ -376,7 +399,7 @@ template <typename T> int enqueue_iter(cgx_cg *cg, int slot) {
     return rc;
   if (sep && (rc = dist_dot<T>(cg, ws->rr_part, npr, &st->rr[slot], slot, 2))) return rc;
   if ((rc = timed(cg, 3, s, [&] {
-         return Launch<T>::update_xp(cg->n, x, p, r, st, slot, ws, sep ? 0 : npr, s, par, far);
+         return Launch<T>::update_xp(cg->n, x, p, r, st, slot, ws, sep ? 0 : npr, s, par3, far);
        })))
     return rc;
   return CGX_OK;
@@ -397,8 +420,9 @@ template <typename T> int enqueue_iter_defer(cgx_cg *cg, int slot) {
   // slower in update_r)
   int rc;
   const int npr = Launch<T>::update_parts(cg->n);
-  // sweep directions: each kernel starts where the previous one ended
-  const int par = cg->altdir ? (slot & 1) : 0, rpar = cg->altdir ? 1 - par : 0;
+  // sweep directions: each kernel starts where the previous one ended (body_dir)
+  const int par = body_dir(cg, slot, 0), rpar = body_dir(cg, slot, 1),
+            par3 = body_dir(cg, slot, 2);
   int npp = 0;
   const PeerDev *far = fused_ar(cg);
   const bool sep = A->dist && !far;  // a separate all-reduce step per dot
@@ -414,7 +438,7 @@ template <typename T> int enqueue_iter_defer(cgx_cg *cg, int slot) {
       return rc;
     return timed(cg, 3, s, [&] {
       return Launch<T>::update_p_defer(cg->n, x, p, pn, P, r, st, slot, ws,
-                                       A->dev.vl_grid, s, par, nullptr);
+                                       A->dev.vl_grid, s, par3, nullptr);
     });
   }
   if ((rc = enqueue_spmv_dot<T>(cg, p, slot, par, &npp))) return rc;
@@ -428,7 +452,7 @@ template <typename T> int enqueue_iter_defer(cgx_cg *cg, int slot) {
     if (sep && (rc = dist_dot_pair<T>(cg, npr, slot))) return rc;
     return timed(cg, 3, s, [&] {
       return Launch<T>::update_p_defer_pc_dist(cg->n, x, p, pn, P, r, m, st, slot, ws, npr, s,
-                                               par, far);
+                                               par3, far);
     });
   }
   if (cg->precond) {  // single device (cgx_cg_set_precond): the SpMV launch is the plain one
@@ -438,7 +462,7 @@ template <typename T> int enqueue_iter_defer(cgx_cg *cg, int slot) {
          })))
       return rc;
     return timed(cg, 3, s, [&] {
-      return Launch<T>::update_p_defer_pc(cg->n, x, p, pn, P, r, m, st, slot, ws, npr, s, par,
+      return Launch<T>::update_p_defer_pc(cg->n, x, p, pn, P, r, m, st, slot, ws, npr, s, par3,
                                           cg->minv_nt);
     });
   }
@@ -451,7 +475,7 @@ template <typename T> int enqueue_iter_defer(cgx_cg *cg, int slot) {
   if (sep && (rc = dist_dot<T>(cg, ws->rr_part, npr, &st->rr[slot], slot, 2))) return rc;
   if ((rc = timed(cg, 3, s, [&] {
          return Launch<T>::update_p_defer(cg->n, x, p, pn, P, r, st, slot, ws, sep ? 0 : npr, s,
-                                          par, far);
+                                          par3, far);
        })))
     return rc;
   return CGX_OK;
@@ -483,7 +507,12 @@ template <typename T> int enqueue_iter_fdefer(cgx_cg *cg, int slot) {
   T *Ap = (T *)cg->Ap, *r = (T *)cg->r, *x = (T *)cg->x;
   int rc;
   const int npr = Launch<T>::update_parts(cg->n);
-  const int par = cg->altdir ? (slot & 1) : 0, rpar = cg->altdir ? 1 - par : 0;
+  // sweep directions (body_dir): on one device the body's two launches run 0, 1
+  // in every slot, so kernel 1 starts where kernel 2 of the body before ended
+  // and kernel 2 where kernel 1 ended, slot 3 -> slot 0 included. The
+  // partitioned body keeps the three-kernel rule's first two directions (it
+  // cannot be measured on one GPU; its walk order is left as it was).
+  const int par = body_dir(cg, slot, 0), rpar = body_dir(cg, slot, 1);
   if (A->dist) {
     // partitioned (dist_fd_ok: device peer transport, lean interior, boundary
     // row blocks): kernel 1 the interior walk with the push of the formed p_k
@@ -616,7 +645,9 @@ int enqueue_iter_any(cgx_cg *cg, int slot) {
 int flush_pending_x(cgx_cg *cg) {
   if (cg->fdefer) {
     // bodies of an unfinished group (a finished one was applied by its slot-3
-    // flush), then the final r.r record when the run ended on an active body
+    // flush), then the final r.r record when the run ended on an active body.
+    // k_flush_defer sweeps forward: on one device every body's last launch
+    // runs direction 1 (body_dir), so the flush too starts where it ended
     hipStream_t s = cg->ctx->stream;
     // (mode 7: kernel 2 is the lean walk, one r.r partial per workgroup)
     const int npr = cg->recompute ? cg->A->dev.vl_grid
@@ -3526,6 +3557,17 @@ extern "C" int cgx_cg_get_mode(cgx_cg *cg, int *mode) {
           : cg->defer     ? 3
           : cg->fused     ? 2
                           : 1;
+  return CGX_OK;
+}
+
+// the directions enqueue_iter_any gives the body in `slot` (body_dir, the
+// enqueue functions' own rule)
+extern "C" int cgx_cg_sweep_dirs(cgx_cg *cg, int slot, int *dirs, int cap, int *n) {
+  CGX_REQUIRE(cg && n && (dirs || cap <= 0), CGX_EINVAL, "NULL argument");
+  CGX_REQUIRE(slot >= 0, CGX_EINVAL, "slot %d", slot);
+  const int m = sweep_rule(cg).directed;
+  *n = m;
+  for (int k = 0; k < m && k < cap; ++k) dirs[k] = body_dir(cg, slot, k);
   return CGX_OK;
 }
 

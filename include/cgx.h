@@ -305,6 +305,18 @@ int cgx_cg_coop_shape(cgx_cg *cg, int *rows_per_thread, int *threads, int *workg
 int cgx_cg_coop_trace(cgx_cg *cg, uint64_t *host, int64_t words);
 /* the iteration structure in effect (1-5; auto resolved) */
 int cgx_cg_get_mode(cgx_cg *cg, int *mode);
+/* The sweep directions (0: rows low to high, 1: high to low) the body in
+ * slot `slot & 3` is enqueued with in the mode in effect, in stream order:
+ * *n = the body's launches that take a direction, dirs[0 .. min(*n, cap) - 1]
+ * filled. The launches alternate in stream order (launch k of the body in
+ * slot s of an L-launch body: (s L + k) & 1), so each starts at the end of the
+ * vectors the launch before it left newest in the caches: three launches
+ * (modes 1, 3, 6; preconditioned and partitioned bodies) s & 1, 1 - (s & 1),
+ * s & 1; the two-kernel bodies on one device (modes 4 and 7) 0, 1 in every
+ * slot. Mode 4 on a partitioned matrix keeps the three-launch rule's first
+ * two (*n = 2). Modes 2 and 5 sweep forward only: *n = 0. Diagnostics: the
+ * directions change no value. */
+int cgx_cg_sweep_dirs(cgx_cg *cg, int slot, int *dirs, int cap, int *n);
 /* mode 4's fused SpMV grid and the SpMV's: where they are equal mode 4 is
  * bit-identical to mode 1, else equal to rounding (one dot's sum order) */
 int cgx_csr_fd_grid(cgx_csr *A, int *fd_grid, int *spmv_grid);
