@@ -83,15 +83,36 @@ struct DeviceGuard {
   explicit DeviceGuard(int dev) { (void)hipSetDevice(dev); }
 };
 
-template <typename T> int enqueue_iter(cgx_cg *cg, int slot);
+// The one fork on the element type: f is called with a float or a double
+// (a tag: its type is the solver's T), and its result is returned
+template <class F> auto with_dtype(int dtype, F &&f) {
+  return dtype == CGX_F32 ? f(float()) : f(double());
+}
+
+// A solver's buffers at their element type
+template <typename T> struct CgView {
+  CgScalars<T> *st;
+  RedWs<T> *ws;
+  T *r, *Ap, *x;
+  T *P[4];     // p, then p buffers 1..3 of the deferred-x modes
+  T *p2;
+  const T *m;  // the preconditioner's diagonal
+  explicit CgView(const cgx_cg *cg)
+      : st((CgScalars<T> *)cg->st), ws((RedWs<T> *)cg->ws), r((T *)cg->r), Ap((T *)cg->Ap),
+        x((T *)cg->x), P{(T *)cg->p, (T *)cg->pk[0], (T *)cg->pk[1], (T *)cg->pk[2]},
+        p2((T *)cg->p2), m((const T *)cg->minv) {}
+};
+
+// where rz starts in the solver's CgScalars<T>
+size_t rz_offset(const cgx_cg *cg) {
+  return with_dtype(cg->dtype, [](auto t) { return offsetof(CgScalars<decltype(t)>, rz); });
+}
 
 int poll_state(cgx_cg *cg, void *h_dst, hipStream_t s) {
   // up to rz (read by cgx_cg_rz alone): the copy's size before preconditioning,
   // within the 256 bytes each of cgx_cg_run's two staging buffers has
-  const size_t bytes =
-      cg->dtype == CGX_F32 ? offsetof(CgScalars<float>, rz) : offsetof(CgScalars<double>, rz);
   static_assert(offsetof(CgScalars<double>, rz) <= 256, "poll staging buffers are 256 bytes");
-  CGX_HIP(hipMemcpyAsync(h_dst, cg->st, bytes, hipMemcpyDeviceToHost, s));
+  CGX_HIP(hipMemcpyAsync(h_dst, cg->st, rz_offset(cg), hipMemcpyDeviceToHost, s));
   return CGX_OK;
 }
 
@@ -105,17 +126,33 @@ struct StateView {
 // (tail_fault: partitioned mode 4's last-workgroup r.r all-reduce timed out —
 // the run stops as on stopped == 3)
 StateView view_state(const cgx_cg *cg, const void *h, int slot) {
-  StateView v{};
-  if (cg->dtype == CGX_F32) {
-    const auto *s = (const CgScalars<float> *)h;
-    v = StateView{s->tail_fault ? 0 : s->active[slot], s->bodies,
-                  s->tail_fault ? 3 : s->stopped, (double)s->rxr[slot]};
-  } else {
-    const auto *s = (const CgScalars<double> *)h;
-    v = StateView{s->tail_fault ? 0 : s->active[slot], s->bodies,
-                  s->tail_fault ? 3 : s->stopped, s->rxr[slot]};
-  }
-  return v;
+  return with_dtype(cg->dtype, [&](auto t) {
+    const auto *s = (const CgScalars<decltype(t)> *)h;
+    return StateView{s->tail_fault ? 0 : s->active[slot], s->bodies,
+                     s->tail_fault ? 3 : s->stopped, (double)s->rxr[slot]};
+  });
+}
+
+// r.r after the last body: it sits in the slot of the first skipped body
+template <typename T> double rxr_after_last(const CgScalars<T> &s) {
+  return (double)s.rxr[s.bodies & 3];
+}
+// ... of the solve in progress, once the stream has drained
+int read_rxr(cgx_cg *cg, double *rxr) {
+  void *h = cg->ctx->h_pinned;
+  if (int rc = poll_state(cg, h, cg->ctx->stream)) return rc;
+  CGX_HIP(hipStreamSynchronize(cg->ctx->stream));
+  *rxr = with_dtype(cg->dtype, [&](auto t) {
+    return rxr_after_last(*(const CgScalars<decltype(t)> *)h);
+  });
+  return CGX_OK;
+}
+
+// the most bodies a solve runs: counter++ < N (CG.hpp:436), or the caller's
+// cap (at least one body)
+long long body_cap(int64_t n_ref, int64_t max_bodies) {
+  const long long cap = (long long)n_ref + 1;
+  return max_bodies < 0 ? cap : std::min<long long>(cap, std::max<long long>(max_bodies, 1));
 }
 
 hipEvent_t next_event(cgx_cg *cg) {
@@ -155,7 +192,9 @@ template <class F> int timed(cgx_cg *cg, int kid, hipStream_t s, F &&launch) {
 // iterations after the stop return at entry and would skew the averages.
 int harvest_events(cgx_cg *cg, int64_t active_iters) {
   int64_t iter_seen = 0;
-  const int last_kid = cg->coop ? 1 : (cg->fused || cg->fdefer) ? 2 : 3;
+  const int last_kid = persistent_body(cg->mode)                      ? 1
+                       : (cg->mode == 2 || two_kernel_body(cg->mode)) ? 2
+                                                                      : 3;
   for (auto &pr : cg->ev_pending) {
     const bool exec = pr.first >= 16;  // the dispatch recorded its own pair too
     const int kid = pr.first & 15;
@@ -173,7 +212,7 @@ int harvest_events(cgx_cg *cg, int64_t active_iters) {
       }
     }
     // (mode 7's slot 3 ends its body with the fused kernel 3 instead of kernel 2)
-    if (kid == last_kid || (kid == 3 && cg->fdefer && cg->recompute)) ++iter_seen;
+    if (kid == last_kid || (kid == 3 && cg->mode == 7)) ++iter_seen;
   }
   cg->ev_pending.clear();
   cg->ev_used = 0;
@@ -185,12 +224,9 @@ int harvest_events(cgx_cg *cg, int64_t active_iters) {
 // interior ones while the exchange is in flight (RCCL on the comm stream),
 // then the boundary ones; otherwise exchange, then one SpMV. *np: partials.
 template <typename T>
-int enqueue_spmv_dot(cgx_cg *cg, T *p, int slot, int rev, int *np) {
+int enqueue_spmv_dot(cgx_cg *cg, const CgView<T> &v, T *p, int slot, int rev, int *np) {
   cgx_csr *A = cg->A;
   hipStream_t s = cg->ctx->stream;
-  auto *st = (CgScalars<T> *)cg->st;
-  auto *ws = (RedWs<T> *)cg->ws;
-  T *Ap = (T *)cg->Ap;
   int rc;
   const bool halo = A->dist && A->halo.n_ghost + A->halo.send_total > 0;
   if (halo && A->peer.on) {
@@ -209,7 +245,7 @@ int enqueue_spmv_dot(cgx_cg *cg, T *p, int slot, int rev, int *np) {
     // boundary workgroups spin on flags raised by the same launch's first
     // workgroups, which relies on their being resident; removed in round 3,
     // DESIGN.md §9)
-    if (!merged && (rc = peer_push<T>(A, p, st, slot, s))) return rc;
+    if (!merged && (rc = peer_push<T>(A, p, v.st, slot, s))) return rc;
     const int gi = !split  ? 0
                    : lean_in ? A->dev.vl_grid
                    : merged  ? Launch<T>::slice_grid_push(A->dev, A->split_ni, wg0)
@@ -225,29 +261,29 @@ int enqueue_spmv_dot(cgx_cg *cg, T *p, int slot, int rev, int *np) {
     if ((rc = timed(cg, 1, s, [&] {
            hipError_t e = hipSuccess;
            if (lean_in)
-             e = Launch<T>::spmv_lean_interior(A->dev, p, Ap, st, slot, ws, s, rev,
+             e = Launch<T>::spmv_lean_interior(A->dev, p, v.Ap, v.st, slot, v.ws, s, rev,
                                                merged ? &A->peer.dev : nullptr, wg0);
            else if (merged)
-             e = Launch<T>::spmv_dot_slices_push(A->dev, A->d_split, A->split_ni, 0, p, Ap, st,
-                                                 slot, ws, s, rev, A->peer.dev, wg0);
+             e = Launch<T>::spmv_dot_slices_push(A->dev, A->d_split, A->split_ni, 0, p, v.Ap, v.st,
+                                                 slot, v.ws, s, rev, A->peer.dev, wg0);
            else if (split)
-             e = Launch<T>::spmv_dot_slices(A->dev, A->d_split, A->split_ni, 0, p, Ap, st, slot,
-                                            ws, s, rev);
+             e = Launch<T>::spmv_dot_slices(A->dev, A->d_split, A->split_ni, 0, p, v.Ap, v.st,
+                                            slot, v.ws, s, rev);
            // the one-waiter form: one workgroup waits, the boundary grid does not
            if (e == hipSuccess && fold && A->peer.one_waiter &&
-               peer_wait_one<T>(A, st, slot, s))
+               peer_wait_one<T>(A, v.st, slot, s))
              e = hipErrorLaunchFailure;
            if (e == hipSuccess && fold)
-             return rows ? Launch<T>::spmv_dot_rows(A->dev, A->d_bnd_blk, A->bnd_nblk, gi, p, Ap,
-                                                    st, slot, ws, s, &A->peer.dev)
+             return rows ? Launch<T>::spmv_dot_rows(A->dev, A->d_bnd_blk, A->bnd_nblk, gi, p, v.Ap,
+                                                    v.st, slot, v.ws, s, &A->peer.dev)
                          : Launch<T>::spmv_dot_slices_bnd(A->dev, A->d_split + A->split_ni,
-                                                          A->split_nb, gi, p, Ap, st, slot, ws, s,
-                                                          rev, A->peer.dev);
-           if (e == hipSuccess && peer_wait<T>(A, p, st, slot, s)) e = hipErrorLaunchFailure;
+                                                          A->split_nb, gi, p, v.Ap, v.st, slot,
+                                                          v.ws, s, rev, A->peer.dev);
+           if (e == hipSuccess && peer_wait<T>(A, p, v.st, slot, s)) e = hipErrorLaunchFailure;
            if (e == hipSuccess)
              e = split ? Launch<T>::spmv_dot_slices(A->dev, A->d_split + A->split_ni, A->split_nb,
-                                                    gi, p, Ap, st, slot, ws, s, rev)
-                       : Launch<T>::spmv_dot(A->dev, p, Ap, st, slot, ws, s, rev);
+                                                    gi, p, v.Ap, v.st, slot, v.ws, s, rev)
+                       : Launch<T>::spmv_dot(A->dev, p, v.Ap, v.st, slot, v.ws, s, rev);
            return e;
          })))
       return rc;
@@ -265,16 +301,16 @@ int enqueue_spmv_dot(cgx_cg *cg, T *p, int slot, int rev, int *np) {
     // one timed region: interior slices, the wait for the halo, boundary slices
     if ((rc = timed(cg, 1, s, [&] {
            hipError_t e =
-               lean_in ? Launch<T>::spmv_lean_interior(A->dev, p, Ap, st, slot, ws, s, rev,
+               lean_in ? Launch<T>::spmv_lean_interior(A->dev, p, v.Ap, v.st, slot, v.ws, s, rev,
                                                        nullptr, 0)
-                       : Launch<T>::spmv_dot_slices(A->dev, A->d_split, A->split_ni, 0, p, Ap,
-                                                    st, slot, ws, s, rev);
+                       : Launch<T>::spmv_dot_slices(A->dev, A->d_split, A->split_ni, 0, p, v.Ap,
+                                                    v.st, slot, v.ws, s, rev);
            if (e == hipSuccess && async) e = hipStreamWaitEvent(s, A->ev_halo, 0);
            if (e == hipSuccess)
-             e = rows ? Launch<T>::spmv_dot_rows(A->dev, A->d_bnd_blk, A->bnd_nblk, gi, p, Ap, st,
-                                                 slot, ws, s, nullptr)
+             e = rows ? Launch<T>::spmv_dot_rows(A->dev, A->d_bnd_blk, A->bnd_nblk, gi, p, v.Ap,
+                                                 v.st, slot, v.ws, s, nullptr)
                       : Launch<T>::spmv_dot_slices(A->dev, A->d_split + A->split_ni, A->split_nb,
-                                                   gi, p, Ap, st, slot, ws, s, rev);
+                                                   gi, p, v.Ap, v.st, slot, v.ws, s, rev);
            return e;
          })))
       return rc;
@@ -283,8 +319,9 @@ int enqueue_spmv_dot(cgx_cg *cg, T *p, int slot, int rev, int *np) {
     return CGX_OK;
   }
   if (halo && (rc = dist_halo_exchange(A, p, s))) return rc;
-  if ((rc = timed(cg, 1, s,
-                  [&] { return Launch<T>::spmv_dot(A->dev, p, Ap, st, slot, ws, s, rev); })))
+  if ((rc = timed(cg, 1, s, [&] {
+         return Launch<T>::spmv_dot(A->dev, p, v.Ap, v.st, slot, v.ws, s, rev);
+       })))
     return rc;
   *np = Launch<T>::spmv_parts(A->dev);
   return CGX_OK;
@@ -294,10 +331,9 @@ int enqueue_spmv_dot(cgx_cg *cg, T *p, int slot, int rev, int *np) {
 // *dst — by the device peer transport in one kernel, or finalized into the
 // scalar ring and all-reduced by the setup transport (RCCL / host).
 template <typename T>
-int dist_dot(cgx_cg *cg, const T *part, int np, T *dst, int slot, int which) {
+int dist_dot(cgx_cg *cg, const CgView<T> &v, const T *part, int np, T *dst, int slot, int which) {
   hipStream_t s = cg->ctx->stream;
-  if (cg->A->peer.on)
-    return peer_allreduce<T>(cg->A, part, np, dst, (CgScalars<T> *)cg->st, slot, s, which);
+  if (cg->A->peer.on) return peer_allreduce<T>(cg->A, part, np, dst, v.st, slot, s, which);
   CGX_HIP(Launch<T>::finalize(part, np, dst, s));
   return dist_allreduce_scalar(cg->ctx, dst, cg->dtype, 1, s);
 }
@@ -307,14 +343,12 @@ int dist_dot(cgx_cg *cg, const T *part, int np, T *dst, int slot, int which) {
 // values (the peer one-waiter form: one k_peer_allreduce2 launch, one tag;
 // host / RCCL: one finalize launch, then one all-reduce with count 2). The
 // plain body's r.r step, with the same number of launches and round trips.
-template <typename T> int dist_dot_pair(cgx_cg *cg, int np, int slot) {
+template <typename T> int dist_dot_pair(cgx_cg *cg, const CgView<T> &v, int np, int slot) {
   hipStream_t s = cg->ctx->stream;
-  auto *st = (CgScalars<T> *)cg->st;
-  auto *ws = (RedWs<T> *)cg->ws;
-  T *dst = &st->rrz[2 * slot];
+  T *dst = &v.st->rrz[2 * slot];
   if (cg->A->peer.on)
-    return peer_allreduce2<T>(cg->A, ws->rr_part, ws->rz_part, np, dst, st, slot, s, 2);
-  CGX_HIP(Launch<T>::finalize2(ws->rr_part, ws->rz_part, np, dst, s));
+    return peer_allreduce2<T>(cg->A, v.ws->rr_part, v.ws->rz_part, np, dst, v.st, slot, s, 2);
+  CGX_HIP(Launch<T>::finalize2(v.ws->rr_part, v.ws->rz_part, np, dst, s));
   return dist_allreduce_scalar(cg->ctx, dst, cg->dtype, 2, s);
 }
 
@@ -339,8 +373,8 @@ struct SweepRule {
   int per_body, directed;
 };
 static SweepRule sweep_rule(const cgx_cg *cg) {
-  if (cg->coop || cg->fused) return {0, 0};
-  if (cg->fdefer) return cg->A->dist ? SweepRule{3, 2} : SweepRule{2, 2};
+  if (cg->mode == 2 || persistent_body(cg->mode)) return {0, 0};
+  if (two_kernel_body(cg->mode)) return cg->A->dist ? SweepRule{3, 2} : SweepRule{2, 2};
   return {3, 3};
 }
 // direction of the k-th directed launch of the body in `slot` (altdir off:
@@ -349,12 +383,18 @@ static int body_dir(const cgx_cg *cg, int slot, int k) {
   return cg->altdir ? sweep_dir(sweep_rule(cg).per_body, slot & 3, k) : 0;
 }
 
-template <typename T> int enqueue_iter(cgx_cg *cg, int slot) {
+// The three-kernel body (modes 1, 3 and 6): the SpMV with p.Ap, the r update,
+// the x/p update. With x deferred (modes 3 and 6) body k uses p buffer k mod 4
+// and writes p_{k+1} into the next one; x is brought up to date in every
+// slot-3 body and at the end of each run (flush_pending_x). Same values as
+// mode 1.
+template <typename T> int enqueue_iter(cgx_cg *cg, const CgView<T> &v, int slot) {
   cgx_csr *A = cg->A;
   hipStream_t s = cg->ctx->stream;
-  auto *st = (CgScalars<T> *)cg->st;
-  auto *ws = (RedWs<T> *)cg->ws;
-  T *p = (T *)cg->p, *Ap = (T *)cg->Ap, *r = (T *)cg->r, *x = (T *)cg->x;
+  const bool defer = defers_x(cg->mode);
+  T *p = v.P[defer ? slot : 0], *pn = v.P[(slot + 1) & 3];
+  // r is updated in place (a ping-pong between two buffers measured 5-9%
+  // slower in update_r, DESIGN.md §5)
   int rc;
   // The dots travel as per-workgroup partials summed by the next kernel
   // (single device). A partitioned run finalizes each local dot into the
@@ -366,119 +406,63 @@ template <typename T> int enqueue_iter(cgx_cg *cg, int slot) {
   int npp = 0;
   const PeerDev *far = fused_ar(cg);
   const bool sep = A->dist && !far;  // a separate all-reduce step per dot
-  if ((rc = enqueue_spmv_dot<T>(cg, p, slot, par, &npp))) return rc;
-  if (cg->precond && A->dist) {
-    // partitioned: the plain partitioned body's steps, with
-    // the r.r all-reduce carrying r.z as its second value (tag base + 2)
-    const T *m = (const T *)cg->minv;
-    if (sep && (rc = dist_dot<T>(cg, ws->pap_part, npp, &st->pAp[slot], slot, 1))) return rc;
-    if ((rc = timed(cg, 2, s, [&] {
-           return Launch<T>::update_r_pc_dist(cg->n, r, Ap, m, st, slot, ws, s, npp, rpar, far);
-         })))
-      return rc;
-    if (sep && (rc = dist_dot_pair<T>(cg, npr, slot))) return rc;
-    return timed(cg, 3, s, [&] {
-      return Launch<T>::update_xp_pc_dist(cg->n, x, p, r, m, st, slot, ws, npr, s, par3, far);
-    });
-  }
-  if (cg->precond) {  // single device (cgx_cg_set_precond): the SpMV launch is the plain one
-    const T *m = (const T *)cg->minv;
-    if ((rc = timed(cg, 2, s, [&] {
-           return Launch<T>::update_r_pc(cg->n, r, Ap, m, st, slot, ws, s, npp, rpar, cg->minv_nt);
-         })))
-      return rc;
-    return timed(cg, 3, s, [&] {
-      return Launch<T>::update_xp_pc(cg->n, x, p, r, m, st, slot, ws, npr, s, par3, cg->minv_nt);
-    });
-  }
-  if (sep && (rc = dist_dot<T>(cg, ws->pap_part, npp, &st->pAp[slot], slot, 1))) return rc;
-  if ((rc = timed(cg, 2, s, [&] {
-         return Launch<T>::update_r(cg->n, r, Ap, st, slot, ws, s, false, sep ? 0 : npp, rpar,
-                                    nullptr, 0, far);
-       })))
-    return rc;
-  if (sep && (rc = dist_dot<T>(cg, ws->rr_part, npr, &st->rr[slot], slot, 2))) return rc;
-  if ((rc = timed(cg, 3, s, [&] {
-         return Launch<T>::update_xp(cg->n, x, p, r, st, slot, ws, sep ? 0 : npr, s, par3, far);
-       })))
-    return rc;
-  return CGX_OK;
-}
-
-// Deferred-x iteration (mode 3): body k uses p buffer k mod 4 and writes
-// p_{k+1} into the next one; x is brought up to date in every slot-3 body
-// and at the end of each run (flush_pending_x). Same values as mode 1.
-template <typename T> int enqueue_iter_defer(cgx_cg *cg, int slot) {
-  cgx_csr *A = cg->A;
-  hipStream_t s = cg->ctx->stream;
-  auto *st = (CgScalars<T> *)cg->st;
-  auto *ws = (RedWs<T> *)cg->ws;
-  T *P[4] = {(T *)cg->p, (T *)cg->pk[0], (T *)cg->pk[1], (T *)cg->pk[2]};
-  T *p = P[slot], *pn = P[(slot + 1) & 3];
-  T *Ap = (T *)cg->Ap, *r = (T *)cg->r, *x = (T *)cg->x;
-  // r is updated in place (a ping-pong between two buffers measured 5-9%
-  // slower in update_r, DESIGN.md §5)
-  int rc;
-  const int npr = Launch<T>::update_parts(cg->n);
-  // sweep directions: each kernel starts where the previous one ended (body_dir)
-  const int par = body_dir(cg, slot, 0), rpar = body_dir(cg, slot, 1),
-            par3 = body_dir(cg, slot, 2);
-  int npp = 0;
-  const PeerDev *far = fused_ar(cg);
-  const bool sep = A->dist && !far;  // a separate all-reduce step per dot
-  if (cg->recompute) {
+  // preconditioned on a single device (cgx_cg_set_precond): the SpMV launch is
+  // the plain one. Partitioned: the plain partitioned body's
+  // steps, with the r.r all-reduce carrying r.z as its second value (tag
+  // base + 2)
+  const bool pc = cg->precond != CGX_PRECOND_NONE, pc_dist = pc && A->dist;
+  int np_rr = sep ? 0 : npr;  // the plain x/p update's r.r partials
+  if (recomputes_ap(cg->mode)) {
     // mode 6: kernel 1 keeps only p.Ap, kernel 2 forms A p again and updates
     // r in the walk's epilogue (no Ap vector: 8 N bytes written and read
-    // less per body), kernel 3 as mode 3's (np_rr: kernel 2's grid)
-    if ((rc = timed(cg, 1, s, [&] { return Launch<T>::lean_dot(A->dev, p, st, slot, ws, s, par); })))
+    // less per body), kernel 3 as mode 3's (np_rr: kernel 2's grid; single
+    // device, so no PeerDev)
+    if ((rc = timed(cg, 1, s,
+                    [&] { return Launch<T>::lean_dot(A->dev, p, v.st, slot, v.ws, s, par); })))
       return rc;
     if ((rc = timed(cg, 2, s, [&] {
-           return Launch<T>::lean_updr(A->dev, p, r, st, slot, ws, s, rpar);
+           return Launch<T>::lean_updr(A->dev, p, v.r, v.st, slot, v.ws, s, rpar);
          })))
       return rc;
-    return timed(cg, 3, s, [&] {
-      return Launch<T>::update_p_defer(cg->n, x, p, pn, P, r, st, slot, ws,
-                                       A->dev.vl_grid, s, par3, nullptr);
-    });
-  }
-  if ((rc = enqueue_spmv_dot<T>(cg, p, slot, par, &npp))) return rc;
-  if (cg->precond && A->dist) {  // partitioned: as enqueue_iter's
-    const T *m = (const T *)cg->minv;
-    if (sep && (rc = dist_dot<T>(cg, ws->pap_part, npp, &st->pAp[slot], slot, 1))) return rc;
+    np_rr = A->dev.vl_grid;
+    far = nullptr;
+  } else {
+    if ((rc = enqueue_spmv_dot<T>(cg, v, p, slot, par, &npp))) return rc;
+    if (sep && (rc = dist_dot<T>(cg, v, v.ws->pap_part, npp, &v.st->pAp[slot], slot, 1)))
+      return rc;
     if ((rc = timed(cg, 2, s, [&] {
-           return Launch<T>::update_r_pc_dist(cg->n, r, Ap, m, st, slot, ws, s, npp, rpar, far);
+           if (pc_dist)
+             return Launch<T>::update_r_pc_dist(cg->n, v.r, v.Ap, v.m, v.st, slot, v.ws, s, npp,
+                                                rpar, far);
+           if (pc)
+             return Launch<T>::update_r_pc(cg->n, v.r, v.Ap, v.m, v.st, slot, v.ws, s, npp, rpar,
+                                           cg->minv_nt);
+           return Launch<T>::update_r(cg->n, v.r, v.Ap, v.st, slot, v.ws, s, false,
+                                      sep ? 0 : npp, rpar, nullptr, 0, far);
          })))
       return rc;
-    if (sep && (rc = dist_dot_pair<T>(cg, npr, slot))) return rc;
-    return timed(cg, 3, s, [&] {
-      return Launch<T>::update_p_defer_pc_dist(cg->n, x, p, pn, P, r, m, st, slot, ws, npr, s,
-                                               par3, far);
-    });
-  }
-  if (cg->precond) {  // single device (cgx_cg_set_precond): the SpMV launch is the plain one
-    const T *m = (const T *)cg->minv;
-    if ((rc = timed(cg, 2, s, [&] {
-           return Launch<T>::update_r_pc(cg->n, r, Ap, m, st, slot, ws, s, npp, rpar, cg->minv_nt);
-         })))
+    if (sep && (rc = pc_dist ? dist_dot_pair<T>(cg, v, npr, slot)
+                             : dist_dot<T>(cg, v, v.ws->rr_part, npr, &v.st->rr[slot], slot, 2)))
       return rc;
-    return timed(cg, 3, s, [&] {
-      return Launch<T>::update_p_defer_pc(cg->n, x, p, pn, P, r, m, st, slot, ws, npr, s, par3,
-                                          cg->minv_nt);
-    });
   }
-  if (sep && (rc = dist_dot<T>(cg, ws->pap_part, npp, &st->pAp[slot], slot, 1))) return rc;
-  if ((rc = timed(cg, 2, s, [&] {
-         return Launch<T>::update_r(cg->n, r, Ap, st, slot, ws, s, false, sep ? 0 : npp, rpar,
-                                    nullptr, 0, far);
-       })))
-    return rc;
-  if (sep && (rc = dist_dot<T>(cg, ws->rr_part, npr, &st->rr[slot], slot, 2))) return rc;
-  if ((rc = timed(cg, 3, s, [&] {
-         return Launch<T>::update_p_defer(cg->n, x, p, pn, P, r, st, slot, ws, sep ? 0 : npr, s,
-                                          par3, far);
-       })))
-    return rc;
-  return CGX_OK;
+  return timed(cg, 3, s, [&] {
+    if (defer && pc_dist)
+      return Launch<T>::update_p_defer_pc_dist(cg->n, v.x, p, pn, v.P, v.r, v.m, v.st, slot, v.ws,
+                                               npr, s, par3, far);
+    if (defer && pc)
+      return Launch<T>::update_p_defer_pc(cg->n, v.x, p, pn, v.P, v.r, v.m, v.st, slot, v.ws, npr,
+                                          s, par3, cg->minv_nt);
+    if (defer)
+      return Launch<T>::update_p_defer(cg->n, v.x, p, pn, v.P, v.r, v.st, slot, v.ws, np_rr, s,
+                                       par3, far);
+    if (pc_dist)
+      return Launch<T>::update_xp_pc_dist(cg->n, v.x, p, v.r, v.m, v.st, slot, v.ws, npr, s, par3,
+                                          far);
+    if (pc)
+      return Launch<T>::update_xp_pc(cg->n, v.x, p, v.r, v.m, v.st, slot, v.ws, npr, s, par3,
+                                     cg->minv_nt);
+    return Launch<T>::update_xp(cg->n, v.x, p, v.r, v.st, slot, v.ws, np_rr, s, par3, far);
+  });
 }
 
 // Mode 4 on a partitioned matrix (enqueue_iter_fdefer's partitioned body):
@@ -498,13 +482,9 @@ bool dist_fd_ok(const cgx_csr *A, int dtype) {
 // body), kernel 2 is update_r with the stop rule; in slot 3 it also applies
 // the group's x updates from the four p buffers (k_update_r_flush). Same
 // values as modes 1 and 3, bit for bit.
-template <typename T> int enqueue_iter_fdefer(cgx_cg *cg, int slot) {
+template <typename T> int enqueue_iter_fdefer(cgx_cg *cg, const CgView<T> &v, int slot) {
   cgx_csr *A = cg->A;
   hipStream_t s = cg->ctx->stream;
-  auto *st = (CgScalars<T> *)cg->st;
-  auto *ws = (RedWs<T> *)cg->ws;
-  T *P[4] = {(T *)cg->p, (T *)cg->pk[0], (T *)cg->pk[1], (T *)cg->pk[2]};
-  T *Ap = (T *)cg->Ap, *r = (T *)cg->r, *x = (T *)cg->x;
   int rc;
   const int npr = Launch<T>::update_parts(cg->n);
   // sweep directions (body_dir): on one device the body's two launches run 0, 1
@@ -513,6 +493,7 @@ template <typename T> int enqueue_iter_fdefer(cgx_cg *cg, int slot) {
   // partitioned body keeps the three-kernel rule's first two directions (it
   // cannot be measured on one GPU; its walk order is left as it was).
   const int par = body_dir(cg, slot, 0), rpar = body_dir(cg, slot, 1);
+  T *pp = v.P[(slot + 3) & 3];  // p_{k-1}
   if (A->dist) {
     // partitioned (dist_fd_ok: device peer transport, lean interior, boundary
     // row blocks): kernel 1 the interior walk with the push of the formed p_k
@@ -525,13 +506,13 @@ template <typename T> int enqueue_iter_fdefer(cgx_cg *cg, int slot) {
     const int wg0 = PD.nsend * kPushWG;
     const int gi = A->dev.vl_grid;
     if ((rc = timed(cg, 1, s, [&] {
-           hipError_t e = Launch<T>::spmv_fd_lean_push(A->dev, r, P[(slot + 3) & 3], P[slot], Ap,
-                                                       st, slot, ws, s, par, PD, wg0);
-           if (e == hipSuccess && A->peer.one_waiter && peer_wait_one<T>(A, st, slot, s))
+           hipError_t e = Launch<T>::spmv_fd_lean_push(A->dev, v.r, pp, v.P[slot], v.Ap, v.st,
+                                                       slot, v.ws, s, par, PD, wg0);
+           if (e == hipSuccess && A->peer.one_waiter && peer_wait_one<T>(A, v.st, slot, s))
              e = hipErrorLaunchFailure;
            if (e == hipSuccess)
-             e = Launch<T>::spmv_fd_rows_bnd(A->dev, A->d_bnd_blk, A->bnd_nblk, gi, r,
-                                             P[(slot + 3) & 3], P[slot], Ap, st, slot, ws, s, PD);
+             e = Launch<T>::spmv_fd_rows_bnd(A->dev, A->d_bnd_blk, A->bnd_nblk, gi, v.r, pp,
+                                             v.P[slot], v.Ap, v.st, slot, v.ws, s, PD);
            return e;
          })))
       return rc;
@@ -540,14 +521,15 @@ template <typename T> int enqueue_iter_fdefer(cgx_cg *cg, int slot) {
     // (the partials in sum_parts order, as kernel 3 would); kernel 3 then
     // reads it from st and only its last workgroup waits (on r.r)
     const bool one = A->peer.one_waiter;
-    if (one && (rc = peer_allreduce<T>(A, ws->pap_part, npp, &st->pAp[slot], st, slot, s, 1)))
+    if (one &&
+        (rc = peer_allreduce<T>(A, v.ws->pap_part, npp, &v.st->pAp[slot], v.st, slot, s, 1)))
       return rc;
     return timed(cg, 2, s, [&] {
-      return Launch<T>::update_r_peer_rule(cg->n, r, Ap, st, slot, ws, one ? 0 : npp, rpar, x,
-                                           slot == 3 ? P : nullptr, s, PD);
+      return Launch<T>::update_r_peer_rule(cg->n, v.r, v.Ap, v.st, slot, v.ws, one ? 0 : npp, rpar,
+                                           v.x, slot == 3 ? v.P : nullptr, s, PD);
     });
   }
-  if (cg->recompute) {
+  if (recomputes_ap(cg->mode)) {
     // mode 7: kernel 1 forms p_k into P[slot] with p.Ap only (the tile walk,
     // no Ap vector), kernel 2 forms A p_k again from it and updates r with
     // the stop rule; in slot 3 its epilogue also applies the group's x
@@ -555,52 +537,50 @@ template <typename T> int enqueue_iter_fdefer(cgx_cg *cg, int slot) {
     // average stays the plain walk's). 58 N bytes per body against mode 6's
     // 66 N.
     if ((rc = timed(cg, 1, s, [&] {
-           return Launch<T>::fd_dot_tile(A->dev, r, P[(slot + 3) & 3], P[slot], st, slot, ws,
+           return Launch<T>::fd_dot_tile(A->dev, v.r, pp, v.P[slot], v.st, slot, v.ws,
                                          A->dev.vl_grid, s, par);
          })))
       return rc;
     if (slot == 3)
       return timed(cg, 3, s, [&] {
-        return Launch<T>::lean_updr_rule_flush(A->dev, r, st, ws, s, rpar, x, P);
+        return Launch<T>::lean_updr_rule_flush(A->dev, v.r, v.st, v.ws, s, rpar, v.x, v.P);
       });
     return timed(cg, 2, s, [&] {
-      return Launch<T>::lean_updr_rule(A->dev, P[slot], r, st, slot, ws, s, rpar);
+      return Launch<T>::lean_updr_rule(A->dev, v.P[slot], v.r, v.st, slot, v.ws, s, rpar);
     });
   }
   const int npp = Launch<T>::fd_parts(A->dev);
   if ((rc = timed(cg, 1, s, [&] {
-         return Launch<T>::spmv_fd(A->dev, r, P[(slot + 3) & 3], P[slot], Ap, st, slot, ws, npr,
-                                   s, par);
+         return Launch<T>::spmv_fd(A->dev, v.r, pp, v.P[slot], v.Ap, v.st, slot, v.ws, npr, s,
+                                   par);
        })))
     return rc;
   // kernel 2: update_r with the stop rule; in slot 3 it also applies the
   // group's deferred x updates (one launch instead of a separate flush)
   if ((rc = timed(cg, 2, s, [&] {
-         return slot == 3 ? Launch<T>::update_r_flush(cg->n, r, Ap, st, slot, ws, npp, rpar, x, P,
-                                                      s)
-                          : Launch<T>::update_r(cg->n, r, Ap, st, slot, ws, s, false, npp, rpar,
-                                                nullptr, 1);
+         return slot == 3 ? Launch<T>::update_r_flush(cg->n, v.r, v.Ap, v.st, slot, v.ws, npp, rpar,
+                                                      v.x, v.P, s)
+                          : Launch<T>::update_r(cg->n, v.r, v.Ap, v.st, slot, v.ws, s, false, npp,
+                                                rpar, nullptr, 1);
        })))
     return rc;
   return CGX_OK;
 }
 
 // Fused iteration (single device): x/p update folded into the next SpMV.
-template <typename T> int enqueue_iter_fused(cgx_cg *cg, int slot) {
+template <typename T> int enqueue_iter_fused(cgx_cg *cg, const CgView<T> &v, int slot) {
   cgx_csr *A = cg->A;
   hipStream_t s = cg->ctx->stream;
-  auto *st = (CgScalars<T> *)cg->st;
-  auto *ws = (RedWs<T> *)cg->ws;
-  T *P[2] = {(T *)cg->p, (T *)cg->p2};
+  T *P[2] = {v.P[0], v.p2};
   T *pp = P[(slot + 3) & 1], *pc = P[slot & 1];
-  T *Ap = (T *)cg->Ap, *r = (T *)cg->r, *x = (T *)cg->x;
   int rc;
   if ((rc = timed(cg, 1, s, [&] {
-         return Launch<T>::spmv_fused(A->dev, r, pp, pc, x, Ap, st, slot, ws, s);
+         return Launch<T>::spmv_fused(A->dev, v.r, pp, pc, v.x, v.Ap, v.st, slot, v.ws, s);
        })))
     return rc;
-  if ((rc = timed(cg, 2, s,
-                  [&] { return Launch<T>::update_r(cg->n, r, Ap, st, slot, ws, s, true); })))
+  if ((rc = timed(cg, 2, s, [&] {
+         return Launch<T>::update_r(cg->n, v.r, v.Ap, v.st, slot, v.ws, s, true);
+       })))
     return rc;
   return CGX_OK;
 }
@@ -612,11 +592,11 @@ int64_t coop_chunk(const cgx_cg *cg) { return (int64_t)cg->poll_every * 8; }
 // Mode 5: `bodies` bodies from `slot` in one persistent launch
 int enqueue_coop(cgx_cg *cg, int slot, int64_t bodies) {
   const CsrDev &A = cg->A->dev;
+  const CgView<double> v(cg);
   const int m = (int)std::min<int64_t>(bodies, 1 << 30);
   return timed(cg, 1, cg->ctx->stream, [&] {
     return cg_coop(cg->n, cg->coop_r, cg->coop_stream, A.rowptr, A.col, (const double *)A.val,
-                   (double *)cg->x, (double *)cg->r, (double *)cg->p, (double *)cg->p2,
-                   (CgScalars<double> *)cg->st, slot, m, (CoopWs *)cg->coop_ws, cg->coop_ticks,
+                   v.x, v.r, v.P[0], v.p2, v.st, slot, m, (CoopWs *)cg->coop_ws, cg->coop_ticks,
                    (unsigned long long *)cg->coop_trace, cg->coop_stall, cg->ctx->stream);
   });
 }
@@ -627,105 +607,75 @@ int coop_want_r() {
   return e ? std::atoi(e) : 0;
 }
 
+// One body of the resolved mode in `slot` (mode 5 has no body of its own to
+// enqueue: enqueue_coop launches a whole chunk)
 int enqueue_iter_any(cgx_cg *cg, int slot) {
-  if (cg->fdefer)
-    return cg->dtype == CGX_F32 ? enqueue_iter_fdefer<float>(cg, slot)
-                                : enqueue_iter_fdefer<double>(cg, slot);
-  if (cg->defer)
-    return cg->dtype == CGX_F32 ? enqueue_iter_defer<float>(cg, slot)
-                                : enqueue_iter_defer<double>(cg, slot);
-  if (cg->fused)
-    return cg->dtype == CGX_F32 ? enqueue_iter_fused<float>(cg, slot)
-                                : enqueue_iter_fused<double>(cg, slot);
-  return cg->dtype == CGX_F32 ? enqueue_iter<float>(cg, slot) : enqueue_iter<double>(cg, slot);
+  return with_dtype(cg->dtype, [&](auto t) {
+    using T = decltype(t);
+    const CgView<T> v(cg);
+    switch (cg->mode) {
+      case 2: return enqueue_iter_fused<T>(cg, v, slot);
+      case 4:
+      case 7: return enqueue_iter_fdefer<T>(cg, v, slot);
+      default: return enqueue_iter<T>(cg, v, slot);  // 1, 3, 6
+    }
+  });
 }
 
 // Fused mode leaves the last body's x update pending, mode 3 up to three:
 // apply them (idempotent).
 int flush_pending_x(cgx_cg *cg) {
-  if (cg->fdefer) {
-    // bodies of an unfinished group (a finished one was applied by its slot-3
-    // flush), then the final r.r record when the run ended on an active body.
-    // k_flush_defer sweeps forward: on one device every body's last launch
-    // runs direction 1 (body_dir), so the flush too starts where it ended
-    hipStream_t s = cg->ctx->stream;
-    // (mode 7: kernel 2 is the lean walk, one r.r partial per workgroup)
-    const int npr = cg->recompute ? cg->A->dev.vl_grid
-                    : cg->dtype == CGX_F32 ? Launch<float>::update_parts(cg->n)
-                                           : Launch<double>::update_parts(cg->n);
-    if (cg->dtype == CGX_F32) {
-      float *P[4] = {(float *)cg->p, (float *)cg->pk[0], (float *)cg->pk[1], (float *)cg->pk[2]};
-      if (cg->slot != 0)
-        CGX_HIP(Launch<float>::flush_defer(cg->n, (float *)cg->x, P, (CgScalars<float> *)cg->st, s));
-      CGX_HIP(Launch<float>::rr_settle((CgScalars<float> *)cg->st, (RedWs<float> *)cg->ws, npr, s));
-    } else {
-      double *P[4] = {(double *)cg->p, (double *)cg->pk[0], (double *)cg->pk[1],
-                      (double *)cg->pk[2]};
-      if (cg->slot != 0)
-        CGX_HIP(Launch<double>::flush_defer(cg->n, (double *)cg->x, P,
-                                            (CgScalars<double> *)cg->st, s));
-      // (partitioned: kernel 3 recorded the world r.r itself)
-      if (!cg->A->dist)
-        CGX_HIP(Launch<double>::rr_settle((CgScalars<double> *)cg->st, (RedWs<double> *)cg->ws,
-                                          npr, s));
-    }
-    return CGX_OK;
-  }
-  if (cg->defer) {
-    hipStream_t s = cg->ctx->stream;
-    if (cg->dtype == CGX_F32) {
-      float *P[4] = {(float *)cg->p, (float *)cg->pk[0], (float *)cg->pk[1], (float *)cg->pk[2]};
-      CGX_HIP(Launch<float>::flush_defer(cg->n, (float *)cg->x, P, (CgScalars<float> *)cg->st, s));
-    } else {
-      double *P[4] = {(double *)cg->p, (double *)cg->pk[0], (double *)cg->pk[1],
-                      (double *)cg->pk[2]};
-      CGX_HIP(Launch<double>::flush_defer(cg->n, (double *)cg->x, P,
-                                          (CgScalars<double> *)cg->st, s));
-    }
-    return CGX_OK;
-  }
-  if (!cg->fused) return CGX_OK;
-  const int last = (cg->slot + 3) & 3;
   hipStream_t s = cg->ctx->stream;
-  void *P[2] = {cg->p, cg->p2};
-  if (cg->dtype == CGX_F32)
-    CGX_HIP(Launch<float>::flush_x(cg->n, (float *)cg->x, (const float *)P[last & 1],
-                                   (CgScalars<float> *)cg->st, last, (RedWs<float> *)cg->ws, s));
-  else
-    CGX_HIP(Launch<double>::flush_x(cg->n, (double *)cg->x, (const double *)P[last & 1],
-                                    (CgScalars<double> *)cg->st, last, (RedWs<double> *)cg->ws,
-                                    s));
-  return CGX_OK;
+  return with_dtype(cg->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    const CgView<T> v(cg);
+    switch (cg->mode) {
+      case 4:
+      case 7: {
+        // bodies of an unfinished group (a finished one was applied by its
+        // slot-3 flush), then the final r.r record when the run ended on an
+        // active body. k_flush_defer sweeps forward: on one device every
+        // body's last launch runs direction 1 (body_dir), so the flush too
+        // starts where it ended
+        // (mode 7: kernel 2 is the lean walk, one r.r partial per workgroup)
+        const int npr = cg->mode == 7 ? cg->A->dev.vl_grid : Launch<T>::update_parts(cg->n);
+        if (cg->slot != 0) CGX_HIP(Launch<T>::flush_defer(cg->n, v.x, v.P, v.st, s));
+        // (partitioned: kernel 3 recorded the world r.r itself)
+        if (!cg->A->dist) CGX_HIP(Launch<T>::rr_settle(v.st, v.ws, npr, s));
+        return CGX_OK;
+      }
+      case 3:
+      case 6: CGX_HIP(Launch<T>::flush_defer(cg->n, v.x, v.P, v.st, s)); return CGX_OK;
+      case 2: {
+        const int last = (cg->slot + 3) & 3;
+        CGX_HIP(Launch<T>::flush_x(cg->n, v.x, last & 1 ? v.p2 : v.P[0], v.st, last, v.ws, s));
+        return CGX_OK;
+      }
+      default: return CGX_OK;
+    }
+  });
 }
 
 // A cached exec may still be in flight (cgx_cg_run keeps two chunks queued):
 // the stream drains before any is destroyed.
-void drop_batch_graph(cgx_cg *cg) {
-  if (cg->bt.graphs.empty()) return;
-  (void)hipStreamSynchronize(cg->ctx->stream);
-  for (auto &kv : cg->bt.graphs) (void)hipGraphExecDestroy(kv.second);
-  cg->bt.graphs.clear();
-}
 // (The batched solver's chunks go where their own inputs change: the poll
 // interval, a preconditioner, the batch's X / ld / width, and with the solver.
 // A single solve on another x, or a change of the single solver's mode, which
 // the batch body does not depend on, leaves them alone.)
-void drop_graph(cgx_cg *cg) {
-  if (cg->graphs.empty()) return;
+void drop_graph(cgx_cg *cg, GraphCache &gc) {
+  if (gc.empty()) return;
   (void)hipStreamSynchronize(cg->ctx->stream);
-  for (auto &kv : cg->graphs) (void)hipGraphExecDestroy(kv.second);
-  cg->graphs.clear();
+  for (auto &kv : gc) (void)hipGraphExecDestroy(kv.second);
+  gc.clear();
 }
 
-// Capture `iters` iterations starting at slot `slot0` (slots slot0 ..
-// slot0 + iters - 1 mod 4) as one graph, cached under (slot0, iters).
-int build_graph(cgx_cg *cg, int slot0, int64_t iters, hipGraphExec_t *out) {
-  if (cg->graph_x != cg->x) drop_graph(cg);
-  hipStream_t s = cg->ctx->stream;
+// Capture `iters` bodies starting at slot `slot0` (slots slot0 ..
+// slot0 + iters - 1 mod 4), each enqueued by body(slot), as one graph.
+template <class F>
+int capture_chunk(hipStream_t s, int slot0, int64_t iters, F &&body, hipGraphExec_t *out) {
   CGX_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   int rc = CGX_OK;
-  for (int64_t i = 0; i < iters && rc == CGX_OK; ++i)
-    rc = enqueue_iter_any(cg, (int)((slot0 + i) & 3));
+  for (int64_t i = 0; i < iters && rc == CGX_OK; ++i) rc = body((int)((slot0 + i) & 3));
   hipGraph_t g = nullptr;
   hipError_t e = hipStreamEndCapture(s, &g);
   if (rc) {
@@ -743,8 +693,6 @@ int build_graph(cgx_cg *cg, int slot0, int64_t iters, hipGraphExec_t *out) {
     (void)hipGraphExecDestroy(ge);
     CGX_HIP(e);
   }
-  cg->graph_x = cg->x;
-  cg->graphs[{slot0, iters}] = ge;
   *out = ge;
   return CGX_OK;
 }
@@ -752,24 +700,100 @@ int build_graph(cgx_cg *cg, int slot0, int64_t iters, hipGraphExec_t *out) {
 bool graph_ok(const cgx_cg *cg) {
   // RCCL / host-transport calls are kept out of captured graphs (the peer
   // transport's iteration is all kernels); timing needs eager launches
-  return cg->use_graph && !cg->timing && !cg->coop && (!cg->A->dist || cg->A->peer.on);
+  return cg->use_graph && !cg->timing && !persistent_body(cg->mode) &&
+         (!cg->A->dist || cg->A->peer.on);
 }
 
 // The graph for a chunk of `iters` bodies from `slot0`: a cached one, else a
 // new capture when `build` (full poll_every chunks, and cgx_cg_prepare),
-// else null (the chunk is launched eagerly).
-int chunk_graph(cgx_cg *cg, int slot0, int64_t iters, bool build, hipGraphExec_t *out) {
+// else null (the chunk is launched eagerly). The caller has dropped a cache
+// that its inputs no longer match (graphs_for_x, cgx_cg_begin_batch).
+template <class F>
+int chunk_graph(cgx_cg *cg, GraphCache &gc, int slot0, int64_t iters, bool build, F &&body,
+                hipGraphExec_t *out) {
   *out = nullptr;
-  if (cg->graph_x == cg->x) {
-    auto it = cg->graphs.find({slot0, iters});
-    if (it != cg->graphs.end()) {
-      *out = it->second;
-      return CGX_OK;
-    }
+  auto it = gc.find({slot0, iters});
+  if (it != gc.end()) {
+    *out = it->second;
+    return CGX_OK;
   }
   if (!build) return CGX_OK;
-  if (cg->graphs.size() >= 16) drop_graph(cg);  // bound the cache
-  return build_graph(cg, slot0, iters, out);
+  if (gc.size() >= 16) drop_graph(cg, gc);  // bound the cache
+  if (int rc = capture_chunk(cg->ctx->stream, slot0, iters, body, out)) return rc;
+  gc[{slot0, iters}] = *out;
+  return CGX_OK;
+}
+
+// The single solver's cache holds chunks captured for x = graph_x
+void graphs_for_x(cgx_cg *cg) {
+  if (cg->graph_x != cg->x) drop_graph(cg, cg->graphs);
+  cg->graph_x = cg->x;
+}
+
+// Queue a chunk of `iters` bodies from `slot0`: its graph replayed when `gc`
+// is given and holds or (a full poll interval) now captures one, else the
+// bodies launched eagerly
+template <class F>
+int enqueue_chunk(cgx_cg *cg, GraphCache *gc, int slot0, int64_t iters, F &&body) {
+  hipGraphExec_t ge = nullptr;
+  int rc = CGX_OK;
+  if (gc && (rc = chunk_graph(cg, *gc, slot0, iters, iters == cg->poll_every, body, &ge)))
+    return rc;
+  if (ge) {
+    CGX_HIP(hipGraphLaunch(ge, cg->ctx->stream));
+    return CGX_OK;
+  }
+  for (int64_t i = 0; i < iters && rc == CGX_OK; ++i) rc = body((int)((slot0 + i) & 3));
+  return rc;
+}
+
+// The chunk pipeline of cgx_cg_run and cgx_cg_run_batch: `bodies` bodies from
+// *slot in chunks, at most two in flight. Behind each chunk a copy of the
+// state into one of two host staging buffers and an event are queued, so
+// chunk c's state is read while chunk c + 1 runs; once a copy shows nothing
+// active no further chunk is queued, and the queued ones are drained.
+//   chunk_size(remaining)  the next chunk's bodies
+//   enqueue(slot0, chunk)  queue the chunk
+//   poll(buf)              queue the state copy into staging buffer buf
+//   read(buf, slot)        read that copy (it has arrived; slot: the one after
+//                          its chunk): is anything still active?
+//   after_last()           once the last chunk and its copy are queued
+template <class Size, class Enq, class Poll, class Read, class Last>
+int run_chunks(cgx_cg *cg, int *slot, int64_t remaining, Size &&chunk_size, Enq &&enqueue,
+               Poll &&poll, Read &&read, Last &&after_last) {
+  hipStream_t s = cg->ctx->stream;
+  hipEvent_t *ev = cg->run_ev;
+  for (int k = 0; k < 2; ++k)
+    if (!ev[k]) CGX_HIP(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+  struct Pending { int buf; int slot_after; };
+  std::vector<Pending> q;
+  int chunk_id = 0, rc = CGX_OK;
+  bool done = false;
+  auto wait_one = [&]() -> int {
+    const Pending pd = q.front();
+    q.erase(q.begin());
+    CGX_HIP(hipEventSynchronize(ev[pd.buf]));
+    if (!read(pd.buf, pd.slot_after)) done = true;
+    return CGX_OK;
+  };
+  while (!done && (remaining > 0 || !q.empty())) {
+    if (remaining > 0 && q.size() < 2) {
+      const int64_t chunk = chunk_size(remaining);
+      if ((rc = enqueue(*slot, chunk))) break;
+      *slot = (int)((*slot + chunk) & 3);
+      remaining -= chunk;
+      const int buf = chunk_id++ & 1;
+      if ((rc = poll(buf))) break;
+      CGX_HIP(hipEventRecord(ev[buf], s));
+      q.push_back(Pending{buf, *slot});
+      if (remaining == 0 && (rc = after_last())) break;
+      continue;
+    }
+    if ((rc = wait_one())) break;
+  }
+  // drain whatever is still queued
+  while (rc == CGX_OK && !q.empty()) rc = wait_one();
+  return rc;
 }
 
 }  // namespace
@@ -3084,7 +3108,6 @@ extern "C" int cgx_cg_create(cgx_ctx *ctx, cgx_csr *A, cgx_cg **out) {
     }
     return hip_fail(e, "cgx_cg_create");
   }
-  cg->fused = false;
   // alternating sweep directions: +0.5-2% at 256^3
   cg->altdir = true;
   *out = cg;
@@ -3092,7 +3115,7 @@ extern "C" int cgx_cg_create(cgx_ctx *ctx, cgx_csr *A, cgx_cg **out) {
   // (mode 3: +4-8% over mode 1 at 256^3) or, where it pays,
   // two (mode 4, fd_auto); plain three kernels when the three extra p buffers
   // do not fit
-  if (cgx_cg_set_mode(cg, 0) != CGX_OK) cg->defer = cg->fdefer = cg->recompute = false;
+  if (cgx_cg_set_mode(cg, 0) != CGX_OK) cg->mode = 1;
   return CGX_OK;
 }
 
@@ -3185,6 +3208,16 @@ static bool coop_auto(const cgx_cg *cg) {
   return A->max_row_nnz <= 7 && coop_rows_per_thread(cg->n, kCoopMaxG) == 1 && coop_fits(cg, 1);
 }
 
+// The preconditioner's mode rule: the preconditioned kernels are modes 1 and
+// 3's (a requested mode may also be 0, auto). false, with the error set, for
+// any other mode.
+static bool precond_mode_ok(int mode) {
+  if (mode == 0 || mode == 1 || mode == 3) return true;
+  set_error("mode %d with a preconditioner: diagonal preconditioning runs in modes 1 and 3 "
+            "(auto resolves to 3)", mode);
+  return false;
+}
+
 extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
   CGX_REQUIRE(cg, CGX_EINVAL, "cg is NULL");
   CGX_REQUIRE(mode >= 0 && mode <= 7, CGX_EINVAL,
@@ -3192,9 +3225,7 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
               "4 fused with deferred x, 5 persistent body, 6 recomputed Ap, 7 fused with "
               "recomputed Ap", mode);
   const int mode_req = mode;
-  CGX_REQUIRE(!cg->precond || mode == 0 || mode == 1 || mode == 3, CGX_EUNSUPPORTED,
-              "mode %d with a preconditioner set: diagonal preconditioning runs in modes 1 and 3 "
-              "(auto resolves to 3)", mode);
+  if (cg->precond && !precond_mode_ok(mode)) return CGX_EUNSUPPORTED;
   CGX_REQUIRE(mode != 6 || (!cg->A->dist && vl_whole(cg->A->dev)), CGX_EUNSUPPORTED,
               "mode 6 (recomputed Ap) needs the lean stencil walk on a single device");
   CGX_REQUIRE(mode != 7 || (!cg->A->dist && cg->dtype == CGX_F64 && lean_tile_ok(cg->A->dev)),
@@ -3239,8 +3270,9 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
               "mode 4 on a partitioned matrix needs f64, the device peer transport and the lean "
               "interior walk with boundary row blocks (partitioned matrices otherwise use mode 1 "
               "or 3)");
-  CGX_REQUIRE(mode != 2 || (cg->dtype == CGX_F32 ? Launch<float>::fused_supported(cg->A->dev)
-                                                 : Launch<double>::fused_supported(cg->A->dev)),
+  CGX_REQUIRE(mode != 2 || with_dtype(cg->dtype, [&](auto t) {
+                return Launch<decltype(t)>::fused_supported(cg->A->dev);
+              }),
               CGX_EUNSUPPORTED, "mode 2 needs a production SpMV format (variant %d has no fused "
               "kernel)", launch_variant(cg->A->dev, cg->dtype));
   CGX_REQUIRE(mode != 4 || cg->A->dist ||
@@ -3272,14 +3304,11 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
       if (cg->dtype == CGX_F64 && lean_ring_ok(cg->A->dev)) mode = 7;
     }
   }
-  const bool f = mode == 2, d = mode == 3 || mode == 6, fd = mode == 4 || mode == 7, c = mode == 5;
-  const bool rc6 = mode == 6 || mode == 7;
-  if (f != cg->fused || d != cg->defer || fd != cg->fdefer || c != cg->coop ||
-      rc6 != cg->recompute) {
+  if (mode != cg->mode) {
     CGX_REQUIRE(!cg->begun, CGX_ESTATE, "set the mode before cgx_cg_begin");
-    drop_graph(cg);
+    drop_graph(cg, cg->graphs);
   }
-  if (c && !cg->coop_ws) {
+  if (mode == 5 && !cg->coop_ws) {
     DeviceGuard g(cg->ctx->device);
     CGX_HIP(hipMalloc(&cg->coop_ws, sizeof(CoopWs)));
     if (const char *e = std::getenv("CGX_COOP_TRACE"); e && std::atoi(e)) {
@@ -3295,12 +3324,12 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
     if (const char *e = std::getenv("CGX_COOP_TIMEOUT_MS"))
       cg->coop_ticks = (long long)clk_khz * std::max(1, std::atoi(e));
   }
-  cg->coop = c;
-  if (c) {
+  if (mode == 5) {
     cg->coop_r = coop_r;
     cg->coop_stream = stream;
   }
-  if ((d || fd) && !cg->pk[0]) {  // three more p buffers (with the ghost tail when partitioned)
+  // three more p buffers (with the ghost tail when partitioned)
+  if (defers_x(mode) && !cg->pk[0]) {
     DeviceGuard g(cg->ctx->device);
     const size_t bytes = (size_t)(cg->n + cg->A->halo.n_ghost) * dtype_size(cg->dtype);
     for (int k = 0; k < 3; ++k) {
@@ -3316,10 +3345,7 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
     }
     CGX_HIP(hipStreamSynchronize(cg->ctx->stream));
   }
-  cg->fused = f;
-  cg->defer = d;
-  cg->fdefer = fd;
-  cg->recompute = rc6;
+  cg->mode = mode;
   cg->mode_req = mode_req;
   return CGX_OK;
 }
@@ -3343,6 +3369,16 @@ template <class F> int pc_scan(cgx_ctx *ctx, unsigned long long (&h)[2], F &&lau
   (void)hipFree(bad);
   CGX_HIP(e);
   return CGX_OK;
+}
+
+// that scan over a caller's diagonal: entries that are not positive and finite
+int minv_scan(cgx_cg *cg, const void *d_minv, unsigned long long (&h)[2]) {
+  return pc_scan(cg->ctx, h, [&](unsigned long long *bad) {
+    return with_dtype(cg->dtype, [&](auto t) {
+      return Launch<decltype(t)>::diag_check(cg->n, (const decltype(t) *)d_minv, bad,
+                                             cg->ctx->stream);
+    });
+  });
 }
 
 // A partitioned matrix: the ranks' verdicts on a scan agreed over the setup
@@ -3438,13 +3474,7 @@ extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
     cgx_csr *A = cg->A;
     const size_t es = dtype_size(cg->dtype);
     unsigned long long h[2] = {0, ~0ull};
-    int rc = CGX_OK, cur = 0;
-    (void)cgx_cg_get_mode(cg, &cur);
-    if (!(cg->mode_req == 0 || cg->mode_req == 1 || cg->mode_req == 3)) {
-      set_error("a preconditioner in mode %d: diagonal preconditioning runs in modes 1 and 3 "
-                "(auto resolves to 3)", cur);
-      rc = CGX_EUNSUPPORTED;
-    }
+    int rc = precond_mode_ok(cg->mode_req) ? CGX_OK : CGX_EUNSUPPORTED;
     if (kind == CGX_PRECOND_JACOBI) {
       if (!rc) {
         hipError_t e = hipMalloc(&own, ((size_t)cg->n + 1) * es);
@@ -3461,12 +3491,7 @@ extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
         set_error("d_minv must be 16-byte aligned (the kernels read it in 16-byte lanes)");
         rc = CGX_EINVAL;
       }
-      if (!rc && cg->n > 0)
-        rc = pc_scan(cg->ctx, h, [&](unsigned long long *bad) {
-          return cg->dtype == CGX_F32
-                     ? Launch<float>::diag_check(cg->n, (const float *)d_minv, bad, s)
-                     : Launch<double>::diag_check(cg->n, (const double *)d_minv, bad, s);
-        });
+      if (!rc && cg->n > 0) rc = minv_scan(cg, d_minv, h);
       rc = pc_agree(A, rc, h, "cgx_cg_set_precond");
       if (!rc && h[0] != 0) {
         set_error("cgx_cg_set_precond: %llu entr%s of d_minv not positive and finite; the first "
@@ -3480,11 +3505,7 @@ extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
       return rc;
     }
   } else if (kind != CGX_PRECOND_NONE) {
-    int cur = 0;
-    (void)cgx_cg_get_mode(cg, &cur);
-    CGX_REQUIRE(cg->mode_req == 0 || cg->mode_req == 1 || cg->mode_req == 3, CGX_EUNSUPPORTED,
-                "a preconditioner in mode %d: diagonal preconditioning runs in modes 1 and 3 "
-                "(auto resolves to 3)", cur);
+    if (!precond_mode_ok(cg->mode_req)) return CGX_EUNSUPPORTED;
     const size_t es = dtype_size(cg->dtype);
     unsigned long long h[2];
     int rc;
@@ -3497,11 +3518,7 @@ extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
       CGX_REQUIRE(d_minv, CGX_EINVAL, "CGX_PRECOND_DIAGONAL needs d_minv");
       CGX_REQUIRE(((uintptr_t)d_minv & 15) == 0, CGX_EINVAL,
                   "d_minv must be 16-byte aligned (the kernels read it in 16-byte lanes)");
-      rc = pc_scan(cg->ctx, h, [&](unsigned long long *bad) {
-        return cg->dtype == CGX_F32
-                   ? Launch<float>::diag_check(cg->n, (const float *)d_minv, bad, s)
-                   : Launch<double>::diag_check(cg->n, (const double *)d_minv, bad, s);
-      });
+      rc = minv_scan(cg, d_minv, h);
       if (!rc && h[0] != 0) {
         set_error("cgx_cg_set_precond: %llu entr%s of d_minv not positive and finite; the first "
                   "is entry %llu", h[0], h[0] == 1 ? "y" : "ies", h[1]);
@@ -3516,8 +3533,8 @@ extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
   }
   // the solve in progress ends here; nothing queued may still read the old m
   CGX_HIP(hipStreamSynchronize(s));
-  drop_graph(cg);
-  drop_batch_graph(cg);
+  drop_graph(cg, cg->graphs);
+  drop_graph(cg, cg->bt.graphs);
   cg->begun = false;
   cg->bt.begun = false;
   if (cg->minv_own) (void)hipFree(cg->minv_own);
@@ -3551,12 +3568,7 @@ extern "C" int cgx_csr_fd_grid(cgx_csr *A, int *fd_grid, int *spmv_grid) {
 
 extern "C" int cgx_cg_get_mode(cgx_cg *cg, int *mode) {
   CGX_REQUIRE(cg && mode, CGX_EINVAL, "NULL argument");
-  *mode = cg->coop       ? 5
-          : cg->fdefer   ? (cg->recompute ? 7 : 4)
-          : cg->recompute ? 6
-          : cg->defer     ? 3
-          : cg->fused     ? 2
-                          : 1;
+  *mode = cg->mode;
   return CGX_OK;
 }
 
@@ -3575,8 +3587,8 @@ extern "C" int cgx_cg_destroy(cgx_cg *cg) {
   if (!cg) return CGX_OK;
   DeviceGuard g(cg->ctx->device);
   (void)hipStreamSynchronize(cg->ctx->stream);
-  drop_graph(cg);
-  drop_batch_graph(cg);
+  drop_graph(cg, cg->graphs);
+  drop_graph(cg, cg->bt.graphs);
   for (auto e : cg->ev_pool) (void)hipEventDestroy(e);
   for (hipEvent_t e : cg->run_ev)
     if (e) (void)hipEventDestroy(e);
@@ -3597,8 +3609,8 @@ extern "C" int cgx_cg_config(cgx_cg *cg, int poll_every, int use_graph) {
   CGX_REQUIRE(cg, CGX_EINVAL, "cg is NULL");
   if (poll_every > 0) {
     if (poll_every != cg->poll_every) {
-      drop_graph(cg);
-      drop_batch_graph(cg);
+      drop_graph(cg, cg->graphs);
+      drop_graph(cg, cg->bt.graphs);
     }
     cg->poll_every = poll_every;
   }
@@ -3615,15 +3627,13 @@ extern "C" int cgx_cg_begin(cgx_cg *cg, const void *b, void *x, double tol,
   DeviceGuard g(cg->ctx->device);
   cgx_csr *A = cg->A;
   hipStream_t s = cg->ctx->stream;
-  const int64_t n_ref = (A->dist ? A->n_global : A->dev.n);
-  long long cap = (long long)n_ref + 1;  // counter++ < N  (CG.hpp:436)
-  if (max_bodies >= 0) cap = std::min<long long>(cap, std::max<long long>(max_bodies, 1));
+  const long long cap = body_cap(A->dist ? A->n_global : A->dev.n, max_bodies);
   cg->b = b;
   cg->x = x;
   cg->bt.begun = false;  // a batch in progress ends here
-  if (cg->fused)  // p_{-1} = 0 for body 0 of the fused iteration
+  if (cg->mode == 2)  // p_{-1} = 0 for body 0 of the fused iteration
     CGX_HIP(hipMemsetAsync(cg->p2, 0, (size_t)cg->n * dtype_size(cg->dtype), s));
-  if (cg->fdefer)  // mode 4: body 0 reads p_{-1} = P[3] (times beta = 0)
+  if (two_kernel_body(cg->mode))  // mode 4: body 0 reads p_{-1} = P[3] (times beta = 0)
     CGX_HIP(hipMemsetAsync(cg->pk[2], 0, (size_t)cg->n * dtype_size(cg->dtype), s));
   const void *xe = x;
   int rc;
@@ -3644,78 +3654,47 @@ extern "C" int cgx_cg_begin(cgx_cg *cg, const void *b, void *x, double tol,
     const size_t es = dtype_size(cg->dtype);
     CGX_HIP(hipMemcpyAsync(cg->Ap, x, (size_t)cg->n * es, hipMemcpyDeviceToDevice, s));
     if (A->peer.on) {
-      rc = cg->dtype == CGX_F32
-               ? peer_push<float>(A, (const float *)cg->Ap, nullptr, 0, s)
-               : peer_push<double>(A, (const double *)cg->Ap, nullptr, 0, s);
-      if (!rc)
-        rc = cg->dtype == CGX_F32 ? peer_wait<float>(A, (float *)cg->Ap, nullptr, 0, s)
-                                  : peer_wait<double>(A, (double *)cg->Ap, nullptr, 0, s);
+      rc = with_dtype(cg->dtype, [&](auto t) {
+        using T = decltype(t);
+        const int rc = peer_push<T>(A, (const T *)cg->Ap, nullptr, 0, s);
+        return rc ? rc : peer_wait<T>(A, (T *)cg->Ap, nullptr, 0, s);
+      });
     } else {
       rc = dist_halo_exchange(A, cg->Ap, s);
     }
     if (rc) return rc;
     xe = cg->Ap;
   }
-  CGX_REQUIRE(!cg->precond || (!cg->fused && !cg->fdefer && !cg->coop && !cg->recompute &&
-                               cg->minv),
-              CGX_ESTATE, "a preconditioner is set but the solver is not in mode 1 or 3");
-  rc = timed(cg, 0, s, [&] {
-    // with a preconditioner a second launch overwrites p = m o r and reduces
-    // rz[0] = r.(m o r) (timed with the init kernel, index 0); on a
-    // partitioned matrix over the own rows, all-reduced below, so the first
-    // body's halo push carries p = m o r
-    if (cg->dtype == CGX_F32) {
-      hipError_t e = Launch<float>::cg_init(A->dev, (const float *)xe, (const float *)b,
-                                            (float *)cg->r, (float *)cg->p,
-                                            (CgScalars<float> *)cg->st, (RedWs<float> *)cg->ws,
-                                            (float)tol, cap, s);
+  if (cg->precond && !precond_mode_ok(cg->mode)) return CGX_ESTATE;
+  rc = with_dtype(cg->dtype, [&](auto t) {
+    using T = decltype(t);
+    const CgView<T> v(cg);
+    int rc = timed(cg, 0, s, [&] {
+      // with a preconditioner a second launch overwrites p = m o r and reduces
+      // rz[0] = r.(m o r) (timed with the init kernel, index 0); on a
+      // partitioned matrix over the own rows, all-reduced below, so the first
+      // body's halo push carries p = m o r
+      hipError_t e = Launch<T>::cg_init(A->dev, (const T *)xe, (const T *)b, v.r, v.P[0], v.st,
+                                        v.ws, (T)tol, cap, s);
       if (e == hipSuccess && cg->precond)
-        e = (A->dist ? Launch<float>::pc_init_dist : Launch<float>::pc_init)(
-            cg->n, (const float *)cg->r, (const float *)cg->minv, (float *)cg->p,
-            (CgScalars<float> *)cg->st, (RedWs<float> *)cg->ws, s);
+        e = (A->dist ? Launch<T>::pc_init_dist : Launch<T>::pc_init)(cg->n, v.r, v.m, v.P[0],
+                                                                     v.st, v.ws, s);
       return e;
+    });
+    if (rc || !A->dist) return rc;
+    if (A->peer.on) {
+      // the init kernel left the local r.r's double-length pair in
+      // rr_part[0..1] (and its value in rxr[0]); all-reduce the pair into rxr[0]
+      rc = peer_allreduce<T>(A, v.ws->rr_part, 1, &v.st->rxr[0], nullptr, 0, s, 0);
+      if (!rc && cg->precond)  // and r.z's pair (k_pc_init_dist) into rz[0]
+        rc = peer_allreduce<T>(A, v.ws->rz_part, 1, &v.st->rz[0], nullptr, 0, s, 0);
+      return rc;
     }
-    hipError_t e = Launch<double>::cg_init(A->dev, (const double *)xe, (const double *)b,
-                                           (double *)cg->r, (double *)cg->p,
-                                           (CgScalars<double> *)cg->st, (RedWs<double> *)cg->ws,
-                                           tol, cap, s);
-    if (e == hipSuccess && cg->precond)
-      e = (A->dist ? Launch<double>::pc_init_dist : Launch<double>::pc_init)(
-          cg->n, (const double *)cg->r, (const double *)cg->minv, (double *)cg->p,
-          (CgScalars<double> *)cg->st, (RedWs<double> *)cg->ws, s);
-    return e;
+    rc = dist_allreduce_scalar(cg->ctx, &v.st->rxr[0], cg->dtype, 1, s);
+    if (!rc && cg->precond) rc = dist_allreduce_scalar(cg->ctx, &v.st->rz[0], cg->dtype, 1, s);
+    return rc;
   });
   if (rc) return rc;
-  if (A->dist && A->peer.on) {
-    // the init kernel left the local r.r's double-length pair in rr_part[0..1]
-    // (and its value in rxr[0]); all-reduce the pair into rxr[0]
-    if (cg->dtype == CGX_F32) {
-      auto *st = (CgScalars<float> *)cg->st;
-      rc = peer_allreduce<float>(A, ((RedWs<float> *)cg->ws)->rr_part, 1, &st->rxr[0], nullptr,
-                                 0, s, 0);
-      if (!rc && cg->precond)  // and r.z's pair (k_pc_init_dist) into rz[0]
-        rc = peer_allreduce<float>(A, ((RedWs<float> *)cg->ws)->rz_part, 1, &st->rz[0], nullptr,
-                                   0, s, 0);
-    } else {
-      auto *st = (CgScalars<double> *)cg->st;
-      rc = peer_allreduce<double>(A, ((RedWs<double> *)cg->ws)->rr_part, 1, &st->rxr[0],
-                                  nullptr, 0, s, 0);
-      if (!rc && cg->precond)
-        rc = peer_allreduce<double>(A, ((RedWs<double> *)cg->ws)->rz_part, 1, &st->rz[0],
-                                    nullptr, 0, s, 0);
-    }
-    if (rc) return rc;
-  } else if (A->dist) {
-    const size_t off = cg->dtype == CGX_F32 ? offsetof(CgScalars<float>, rxr)
-                                            : offsetof(CgScalars<double>, rxr);
-    if ((rc = dist_allreduce_scalar(cg->ctx, (char *)cg->st + off, cg->dtype, 1, s))) return rc;
-    if (cg->precond) {
-      const size_t offz = cg->dtype == CGX_F32 ? offsetof(CgScalars<float>, rz)
-                                               : offsetof(CgScalars<double>, rz);
-      if ((rc = dist_allreduce_scalar(cg->ctx, (char *)cg->st + offz, cg->dtype, 1, s)))
-        return rc;
-    }
-  }
   cg->slot = 0;
   cg->begun = true;
   return CGX_OK;
@@ -3726,36 +3705,16 @@ extern "C" int cgx_cg_run(cgx_cg *cg, int64_t bodies, int64_t *bodies_total, int
   CGX_REQUIRE(cg->begun, CGX_ESTATE, "cgx_cg_run before cgx_cg_begin");
   DeviceGuard g(cg->ctx->device);
   hipStream_t s = cg->ctx->stream;
-  const bool use_graph = graph_ok(cg);
-  if (cg->graph_x != cg->x) drop_graph(cg);
+  const bool coop = persistent_body(cg->mode);
+  GraphCache *gc = graph_ok(cg) ? &cg->graphs : nullptr;
+  graphs_for_x(cg);
   // Two host staging buffers: chunk c's state is read while chunk c+1 runs.
   auto *hbuf = (char *)cg->ctx->h_pinned;
-  for (int k = 0; k < 2; ++k)
-    if (!cg->run_ev[k]) CGX_HIP(hipEventCreateWithFlags(&cg->run_ev[k], hipEventDisableTiming));
-  hipEvent_t *ev = cg->run_ev;
-  struct Pending { int buf; int slot_after; int64_t iters; };
-  std::vector<Pending> q;
-  int64_t remaining = bodies;
-  int chunk_id = 0, rc = CGX_OK;
-  bool done = false;
+  int rc = CGX_OK;
   long long last_bodies = -1;
   int last_stopped = 0;
   long long bodies_before = -1;
   bool flushed = false;
-  auto wait_one = [&]() -> int {
-    Pending pd = q.front();
-    q.erase(q.begin());
-    CGX_HIP(hipEventSynchronize(ev[pd.buf]));
-    StateView v = view_state(cg, hbuf + 256 * pd.buf, pd.slot_after);
-    if (cg->timing) {
-      const long long before = bodies_before < 0 ? 0 : bodies_before;
-      (void)before;
-    }
-    last_bodies = v.bodies;
-    last_stopped = v.stopped;
-    if (!v.active) done = true;
-    return CGX_OK;
-  };
   // bodies executed before this call (for the timing harvest)
   if (cg->timing) {
     CGX_HIP(hipStreamSynchronize(s));
@@ -3764,42 +3723,38 @@ extern "C" int cgx_cg_run(cgx_cg *cg, int64_t bodies, int64_t *bodies_total, int
     bodies_before = view_state(cg, hbuf, cg->slot).bodies;
     // an init kernel may still be pending in the event list
   }
-  while (!done && (remaining > 0 || !q.empty())) {
-    if (remaining > 0 && q.size() < 2) {
+  // modes 3 / 6 apply a group's x updates in its slot-3 body (the two-kernel
+  // modes' end-of-run flush also settles r.r, so they flush at any slot)
+  const bool group_flush = defers_x(cg->mode) && !two_kernel_body(cg->mode);
+  rc = run_chunks(
+      cg, &cg->slot, bodies,
       // mode 5: one launch per chunk of coop_chunk bodies (it leaves at the stop)
-      const int64_t chunk = std::min<int64_t>(remaining, cg->coop ? coop_chunk(cg) : cg->poll_every);
-      hipGraphExec_t ge = nullptr;
-      if (use_graph && (rc = chunk_graph(cg, cg->slot, chunk, chunk == cg->poll_every, &ge))) break;
-      if (cg->coop) {
-        if ((rc = enqueue_coop(cg, cg->slot, chunk))) break;
-      } else if (ge) {
-        CGX_HIP(hipGraphLaunch(ge, s));
-      } else {
-        for (int64_t i = 0; i < chunk && rc == CGX_OK; ++i) rc = enqueue_iter_any(cg, (cg->slot + (int)i) & 3);
-        if (rc) break;
-      }
-      cg->slot = (int)((cg->slot + chunk) & 3);
-      remaining -= chunk;
-      const int buf = chunk_id++ & 1;
-      if ((rc = poll_state(cg, hbuf + 256 * buf, s))) break;
-      CGX_HIP(hipEventRecord(ev[buf], s));
-      q.push_back(Pending{buf, cg->slot, chunk});
-      if (remaining == 0 && !cg->A->dist && !cg->coop && !(cg->defer && cg->slot == 0)) {
+      [&](int64_t remaining) {
+        return std::min<int64_t>(remaining, coop ? coop_chunk(cg) : cg->poll_every);
+      },
+      [&](int slot0, int64_t chunk) {
+        if (coop) return enqueue_coop(cg, slot0, chunk);
+        return enqueue_chunk(cg, gc, slot0, chunk,
+                             [&](int slot) { return enqueue_iter_any(cg, slot); });
+      },
+      [&](int buf) { return poll_state(cg, hbuf + 256 * buf, s); },
+      [&](int buf, int slot_after) {
+        const StateView v = view_state(cg, hbuf + 256 * buf, slot_after);
+        last_bodies = v.bodies;
+        last_stopped = v.stopped;
+        return v.active != 0;
+      },
+      [&]() -> int {
         // the end-of-run x flush reads only device state and the slot, so a
         // single-device run queues it behind its last chunk instead of after
         // the host has seen that chunk finish (one host round trip less).
         // (Modes 3 / 6 ending at slot 0: the slot-3 body applied the group, so
         // the flush is needed only if the run stopped inside the group; the
         // host decides once it has read the state below)
-        if ((rc = flush_pending_x(cg))) break;
+        if (cg->A->dist || coop || (group_flush && cg->slot == 0)) return CGX_OK;
         flushed = true;
-      }
-      continue;
-    }
-    if ((rc = wait_one())) break;
-  }
-  // drain whatever is still queued
-  while (rc == CGX_OK && !q.empty()) rc = wait_one();
+        return flush_pending_x(cg);
+      });
   if (rc) return rc;
   if (last_stopped == 3) {
     set_error("peer transport: a device-side wait timed out (a rank stopped responding, or "
@@ -3812,7 +3767,7 @@ extern "C" int cgx_cg_run(cgx_cg *cg, int64_t bodies, int64_t *bodies_total, int
     return CGX_EHIP;
   }
   // (modes 3 / 6 at slot 0 with every body active: the group is applied)
-  const bool applied = cg->defer && cg->slot == 0 && last_stopped == 0 && !cg->A->dist;
+  const bool applied = group_flush && cg->slot == 0 && last_stopped == 0 && !cg->A->dist;
   if (!flushed && !applied && (rc = flush_pending_x(cg))) return rc;
   CGX_HIP(hipStreamSynchronize(s));
   if (cg->timing) {
@@ -3830,13 +3785,15 @@ extern "C" int cgx_cg_prepare(cgx_cg *cg, int64_t bodies) {
   CGX_REQUIRE(cg->begun, CGX_ESTATE, "cgx_cg_prepare before cgx_cg_begin");
   if (!graph_ok(cg) || bodies < 1) return CGX_OK;
   DeviceGuard g(cg->ctx->device);
-  if (cg->graph_x != cg->x) drop_graph(cg);
+  graphs_for_x(cg);
   // the chunk sequence cgx_cg_run(bodies) walks from the current slot
   int slot = cg->slot;
   for (int64_t remaining = bodies; remaining > 0;) {
     const int64_t chunk = std::min<int64_t>(remaining, cg->poll_every);
     hipGraphExec_t ge = nullptr;
-    if (int rc = chunk_graph(cg, slot, chunk, true, &ge)) return rc;
+    if (int rc = chunk_graph(cg, cg->graphs, slot, chunk, true,
+                             [&](int sl) { return enqueue_iter_any(cg, sl); }, &ge))
+      return rc;
     slot = (int)((slot + chunk) & 3);
     remaining -= chunk;
   }
@@ -3847,7 +3804,7 @@ extern "C" int cgx_cg_coop_shape(cgx_cg *cg, int *rows_per_thread, int *threads,
                                  int *workgroups, int *form) {
   CGX_REQUIRE(cg && rows_per_thread && threads && workgroups && form, CGX_EINVAL,
               "NULL argument");
-  CGX_REQUIRE(cg->coop, CGX_ESTATE, "the solver is not in mode 5");
+  CGX_REQUIRE(persistent_body(cg->mode), CGX_ESTATE, "the solver is not in mode 5");
   *rows_per_thread = cg->coop_r;
   *threads = 1024;
   const int64_t per = (int64_t)*threads * cg->coop_r;
@@ -3870,14 +3827,7 @@ extern "C" int cgx_cg_rxr(cgx_cg *cg, double *rxr) {
   CGX_REQUIRE(cg && rxr, CGX_EINVAL, "NULL argument");
   CGX_REQUIRE(cg->begun, CGX_ESTATE, "cgx_cg_rxr before cgx_cg_begin");
   DeviceGuard g(cg->ctx->device);
-  auto *h = (char *)cg->ctx->h_pinned;
-  int rc;
-  if ((rc = poll_state(cg, h, cg->ctx->stream))) return rc;
-  CGX_HIP(hipStreamSynchronize(cg->ctx->stream));
-  // the rxr after the last body sits in the slot of the first skipped body
-  const long long bodies = view_state(cg, h, 0).bodies;
-  *rxr = view_state(cg, h, (int)(bodies & 3)).rxr;
-  return CGX_OK;
+  return read_rxr(cg, rxr);
 }
 
 extern "C" int cgx_cg_rz(cgx_cg *cg, double *rz) {
@@ -3890,14 +3840,13 @@ extern "C" int cgx_cg_rz(cgx_cg *cg, double *rz) {
   int rc;
   if ((rc = poll_state(cg, h, s))) return rc;
   // rz lies past the polled part of the scalars: into the staging buffer's tail
-  const bool f32 = cg->dtype == CGX_F32;
-  const size_t off = f32 ? offsetof(CgScalars<float>, rz) : offsetof(CgScalars<double>, rz);
-  CGX_HIP(hipMemcpyAsync(h + 256, (const char *)cg->st + off, 4 * dtype_size(cg->dtype),
+  CGX_HIP(hipMemcpyAsync(h + 256, (const char *)cg->st + rz_offset(cg), 4 * dtype_size(cg->dtype),
                          hipMemcpyDeviceToHost, s));
   CGX_HIP(hipStreamSynchronize(s));
   // as rxr: the value after the last body sits in the slot of the first skipped body
   const int slot = (int)(view_state(cg, h, 0).bodies & 3);
-  *rz = f32 ? (double)((const float *)(h + 256))[slot] : ((const double *)(h + 256))[slot];
+  *rz = with_dtype(cg->dtype,
+                   [&](auto t) { return (double)((const decltype(t) *)(h + 256))[slot]; });
   return CGX_OK;
 }
 
@@ -3905,20 +3854,12 @@ extern "C" int cgx_cg_solve(cgx_cg *cg, const void *b, void *x, double tol, int6
                             int64_t *bodies_out, double *rxr_out) {
   int rc = cgx_cg_begin(cg, b, x, tol, max_bodies);
   if (rc) return rc;
-  const int64_t n_ref = cg->A->dist ? cg->A->n_global : cg->n;
-  int64_t cap = n_ref + 1;
-  if (max_bodies >= 0) cap = std::min<int64_t>(cap, std::max<int64_t>(max_bodies, 1));
+  const int64_t cap = body_cap(cg->A->dist ? cg->A->n_global : cg->n, max_bodies);
   int64_t total = 0;
   int stopped = 0;
   if ((rc = cgx_cg_run(cg, cap, &total, &stopped))) return rc;
   DeviceGuard g(cg->ctx->device);
-  if (rxr_out) {
-    // the rxr after the last body sits in the slot of the first skipped body
-    auto *h = (char *)cg->ctx->h_pinned;
-    if ((rc = poll_state(cg, h, cg->ctx->stream))) return rc;
-    CGX_HIP(hipStreamSynchronize(cg->ctx->stream));
-    *rxr_out = view_state(cg, h, (int)(total & 3)).rxr;
-  }
+  if (rxr_out && (rc = read_rxr(cg, rxr_out))) return rc;
   if (bodies_out) *bodies_out = total;
   return CGX_OK;
 }
@@ -3954,7 +3895,7 @@ int batch_alloc(cgx_cg *cg, int width) {
   hipStream_t s = cg->ctx->stream;
   if (b.width != width) {
     CGX_HIP(hipStreamSynchronize(s));
-    drop_batch_graph(cg);
+    drop_graph(cg, b.graphs);
     for (void **v : {&b.r, &b.p, &b.Ap}) {
       if (*v) CGX_HIP(hipFree(*v));
       *v = nullptr;
@@ -3993,48 +3934,17 @@ int enqueue_iter_batch(cgx_cg *cg, int slot) {
   return CGX_OK;
 }
 
-// the graph of a chunk of `iters` bodies from slot0 (as chunk_graph: cached,
-// else captured when `build`, else null and the chunk is launched eagerly)
-int batch_chunk_graph(cgx_cg *cg, int slot0, int64_t iters, bool build, hipGraphExec_t *out) {
-  auto &b = cg->bt;
-  *out = nullptr;
-  auto it = b.graphs.find({slot0, iters});
-  if (it != b.graphs.end()) {
-    *out = it->second;
-    return CGX_OK;
-  }
-  if (!build) return CGX_OK;
-  if (b.graphs.size() >= 16) drop_batch_graph(cg);
-  hipStream_t s = cg->ctx->stream;
-  CGX_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  int rc = CGX_OK;
-  for (int64_t i = 0; i < iters && rc == CGX_OK; ++i)
-    rc = enqueue_iter_batch(cg, (int)((slot0 + i) & 3));
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(s, &g);
-  if (rc) {
-    if (g) (void)hipGraphDestroy(g);
-    return rc;
-  }
-  CGX_HIP(e);
-  hipGraphExec_t ge = nullptr;
-  e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  CGX_HIP(e);
-  if ((e = hipGraphUpload(ge, s)) != hipSuccess) {
-    (void)hipGraphExecDestroy(ge);
-    CGX_HIP(e);
-  }
-  b.graphs[{slot0, iters}] = ge;
-  *out = ge;
-  return CGX_OK;
-}
-
 // the nrhs scalar rings into h (asynchronous)
 int batch_poll(cgx_cg *cg, void *h, hipStream_t s) {
   CGX_HIP(hipMemcpyAsync(h, cg->bt.st, (size_t)cg->bt.nrhs * sizeof(BSt), hipMemcpyDeviceToHost,
                          s));
   return CGX_OK;
+}
+// a batch goes on while any column is active in `slot`
+bool batch_active(const BSt *st, int nrhs, int slot) {
+  bool any = false;
+  for (int c = 0; c < nrhs; ++c) any = any || st[c].active[slot] != 0;
+  return any;
 }
 
 int batch_check_args(cgx_cg *cg, int nrhs, const void *B, int64_t ldb, const void *X, int64_t ldx) {
@@ -4080,13 +3990,12 @@ extern "C" int cgx_cg_begin_batch(cgx_cg *cg, int nrhs, const void *d_B, int64_t
   DeviceGuard g(cg->ctx->device);
   hipStream_t s = cg->ctx->stream;
   auto &b = cg->bt;
-  long long cap = (long long)cg->n + 1;  // as cgx_cg_begin
-  if (max_bodies >= 0) cap = std::min<long long>(cap, std::max<long long>(max_bodies, 1));
+  const long long cap = body_cap(cg->n, max_bodies);
   cg->begun = false;  // a single solve in progress ends here
   b.begun = false;
   const int width = Launch<double>::batch_width(nrhs);
   if (int rc = batch_alloc(cg, width)) return rc;
-  if (b.graph_x != d_X || b.graph_ldx != ldx || b.graph_w != width) drop_batch_graph(cg);
+  if (b.graph_x != d_X || b.graph_ldx != ldx || b.graph_w != width) drop_graph(cg, b.graphs);
   b.graph_x = d_X;
   b.graph_ldx = ldx;
   b.graph_w = width;
@@ -4116,50 +4025,20 @@ extern "C" int cgx_cg_run_batch(cgx_cg *cg, int64_t bodies, int64_t *bodies_tota
   auto &b = cg->bt;
   const size_t hb = kBatchMax * sizeof(BSt);
   auto *hbuf = (char *)b.h_poll;
-  for (int k = 0; k < 2; ++k)
-    if (!cg->run_ev[k]) CGX_HIP(hipEventCreateWithFlags(&cg->run_ev[k], hipEventDisableTiming));
-  hipEvent_t *ev = cg->run_ev;
-  struct Pending { int buf; int slot_after; };
-  std::vector<Pending> q;
-  int64_t remaining = std::max<int64_t>(bodies, 0);
-  int chunk_id = 0, rc = CGX_OK, last_buf = -1;
-  bool done = false;
-  auto wait_one = [&]() -> int {
-    const Pending pd = q.front();
-    q.erase(q.begin());
-    CGX_HIP(hipEventSynchronize(ev[pd.buf]));
-    const auto *st = (const BSt *)(hbuf + hb * pd.buf);
-    bool any = false;
-    for (int c = 0; c < b.nrhs; ++c) any = any || st[c].active[pd.slot_after] != 0;
-    if (!any) done = true;
-    last_buf = pd.buf;
-    return CGX_OK;
-  };
-  while (!done && (remaining > 0 || !q.empty())) {
-    if (remaining > 0 && q.size() < 2) {
-      const int64_t chunk = std::min<int64_t>(remaining, cg->poll_every);
-      hipGraphExec_t ge = nullptr;
-      if (cg->use_graph &&
-          (rc = batch_chunk_graph(cg, b.slot, chunk, chunk == cg->poll_every, &ge)))
-        break;
-      if (ge) {
-        CGX_HIP(hipGraphLaunch(ge, s));
-      } else {
-        for (int64_t i = 0; i < chunk && rc == CGX_OK; ++i)
-          rc = enqueue_iter_batch(cg, (b.slot + (int)i) & 3);
-        if (rc) break;
-      }
-      b.slot = (int)((b.slot + chunk) & 3);
-      remaining -= chunk;
-      const int buf = chunk_id++ & 1;
-      if ((rc = batch_poll(cg, hbuf + hb * buf, s))) break;
-      CGX_HIP(hipEventRecord(ev[buf], s));
-      q.push_back(Pending{buf, b.slot});
-      continue;
-    }
-    if ((rc = wait_one())) break;
-  }
-  while (rc == CGX_OK && !q.empty()) rc = wait_one();
+  int last_buf = -1;
+  int rc = run_chunks(
+      cg, &b.slot, std::max<int64_t>(bodies, 0),
+      [&](int64_t remaining) { return std::min<int64_t>(remaining, cg->poll_every); },
+      [&](int slot0, int64_t chunk) {
+        return enqueue_chunk(cg, cg->use_graph ? &b.graphs : nullptr, slot0, chunk,
+                             [&](int slot) { return enqueue_iter_batch(cg, slot); });
+      },
+      [&](int buf) { return batch_poll(cg, hbuf + hb * buf, s); },
+      [&](int buf, int slot_after) {
+        last_buf = buf;
+        return batch_active((const BSt *)(hbuf + hb * buf), b.nrhs, slot_after);
+      },
+      [] { return CGX_OK; });
   if (rc) return rc;
   if (last_buf < 0) {  // no body asked for: the state as it stands
     if ((rc = batch_poll(cg, hbuf, s))) return rc;
@@ -4167,12 +4046,8 @@ extern "C" int cgx_cg_run_batch(cgx_cg *cg, int64_t bodies, int64_t *bodies_tota
   }
   CGX_HIP(hipStreamSynchronize(s));
   const auto *st = (const BSt *)(hbuf + hb * last_buf);
-  bool any = false;
-  for (int c = 0; c < b.nrhs; ++c) {
-    if (bodies_total) bodies_total[c] = st[c].bodies;
-    any = any || st[c].active[b.slot] != 0;
-  }
-  if (all_stopped) *all_stopped = any ? 0 : 1;
+  for (int c = 0; c < b.nrhs && bodies_total; ++c) bodies_total[c] = st[c].bodies;
+  if (all_stopped) *all_stopped = batch_active(st, b.nrhs, b.slot) ? 0 : 1;
   return CGX_OK;
 }
 
@@ -4181,8 +4056,7 @@ extern "C" int cgx_cg_solve_batch(cgx_cg *cg, int nrhs, const void *d_B, int64_t
                                   int64_t *bodies_out, double *rxr_out, int *stopped_out) {
   if (int rc = batch_check_args(cg, nrhs, d_B, ldb, d_X, ldx)) return rc;
   CGX_REQUIRE(bodies_out && rxr_out, CGX_EINVAL, "bodies_out or rxr_out is NULL");
-  int64_t cap = cg->n + 1;
-  if (max_bodies >= 0) cap = std::min<int64_t>(cap, std::max<int64_t>(max_bodies, 1));
+  const int64_t cap = body_cap(cg->n, max_bodies);
   cg->bt.last_form = batch_form_in_effect(cg, nrhs);
   if (cg->bt.last_form == 1) {
     int rc = cgx_cg_begin_batch(cg, nrhs, d_B, ldb, d_X, ldx, tol, max_bodies);
@@ -4195,9 +4069,8 @@ extern "C" int cgx_cg_solve_batch(cgx_cg *cg, int nrhs, const void *d_B, int64_t
     CGX_HIP(hipStreamSynchronize(s));
     const auto *st = (const BSt *)cg->bt.h_poll;
     for (int c = 0; c < nrhs; ++c) {
-      // the rxr after the last body sits in the slot of the first skipped body
       bodies_out[c] = st[c].bodies;
-      rxr_out[c] = st[c].rxr[st[c].bodies & 3];
+      rxr_out[c] = rxr_after_last(st[c]);
       if (stopped_out) stopped_out[c] = st[c].stopped;
     }
     return CGX_OK;

@@ -43,7 +43,7 @@ template <typename T> struct CgScalars {
   // workgroup timed out (written by that workgroup only: stopped and active
   // belong to workgroup 0 of the same launch); the host stops as on 3
   int tail_fault;
-  // deferred x update (mode 3, cgx_abi.cpp enqueue_iter_defer): alpha of the
+  // deferred x update (mode 3, cgx_abi.cpp enqueue_iter): alpha of the
   // body in slot s, set by its update_r; ran[s]: the body ran and its x
   // update is not applied yet (set by its update_xp, cleared by the slot-3
   // flush); skip[s]: an end-of-run flush already applied it (cleared by the

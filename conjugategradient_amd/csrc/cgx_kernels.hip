@@ -3180,7 +3180,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_lean(CsrArgs A, const T *__rest
   store_part(ws->pap_part, A.part_off + blockIdx.x - A.wg0, e.acc, sm.red);
 }
 
-// Recomputed-Ap body (mode 6; cgx_abi.cpp enqueue_iter_defer), kernel 1 of
+// Recomputed-Ap body (mode 6; cgx_abi.cpp enqueue_iter), kernel 1 of
 // 3: the lean walk's A p with only p.Ap kept (no Ap stored: 8 N bytes less
 // written, and kernel 2 reads p instead of Ap, which the walk just pulled
 // through the Infinity Cache)

@@ -221,6 +221,23 @@ struct cgx_csr {
   std::chrono::steady_clock::time_point setup_last{};
 };
 
+namespace cgx {
+// Captured chunks of CG bodies, keyed by (first slot, bodies): full chunks of
+// `poll_every` from any slot (built on first use) and the chunks
+// cgx_cg_prepare built ahead of a run; at most 16 (cgx_abi.cpp chunk_graph)
+using GraphCache = std::map<std::pair<int, int64_t>, hipGraphExec_t>;
+
+// What a resolved mode (cgx_cg::mode) says of its body:
+// x updated once per 4 bodies, from 4 p buffers
+inline bool defers_x(int mode) { return mode == 3 || mode == 4 || mode == 6 || mode == 7; }
+// two kernels per body: the p update folded into the SpMV, x deferred
+inline bool two_kernel_body(int mode) { return mode == 4 || mode == 7; }
+// Ap formed again in the r update's walk, not stored
+inline bool recomputes_ap(int mode) { return mode == 6 || mode == 7; }
+// one launch per chunk (cgx_coop.hip)
+inline bool persistent_body(int mode) { return mode == 5; }
+}  // namespace cgx
+
 struct cgx_cg {
   cgx_ctx *ctx = nullptr;
   cgx_csr *A = nullptr;
@@ -228,12 +245,11 @@ struct cgx_cg {
   int64_t n = 0;
   void *r = nullptr, *p = nullptr, *Ap = nullptr;  // p, Ap: n + n_ghost
   void *p2 = nullptr;   // second p buffer of the fused iteration (single device)
-  bool fused = false;   // two kernels per iteration (x/p update folded into SpMV)
-  bool defer = false;   // mode 3: x updated once per 4 bodies from 4 p buffers
-  bool fdefer = false;  // mode 4: p update folded into the SpMV, x deferred as mode 3
-  bool recompute = false;  // mode 6 (with defer): Ap formed again in update_r's walk, not stored
-  bool coop = false;    // mode 5: persistent body, one launch per chunk (cgx_coop.hip)
-  int coop_r = 0;       // its rows per thread
+  // the resolved mode, 1-7 (cgx_cg_set_mode; cgx.h): 1 three kernels per body,
+  // 2 two (x/p update folded into SpMV), 3 as 1 with x deferred, 4 two kernels
+  // with x deferred, 5 the persistent body, 6 and 7 as 3 and 4 with Ap recomputed
+  int mode = 1;
+  int coop_r = 0;       // mode 5's rows per thread
   int coop_stall = -1;  // tests: a launch's body whose p.Ap partial workgroup 0
                         // withholds ($CGX_COOP_INJECT_STALL; -1 none)
   void *coop_ws = nullptr;  // cgx::CoopWs
@@ -258,10 +274,7 @@ struct cgx_cg {
   bool begun = false;
   int poll_every = 32;
   bool use_graph = true;
-  // captured iterations, keyed by (first slot, bodies): full chunks of
-  // `poll_every` from any slot (built on first use) and the chunks
-  // cgx_cg_prepare built ahead of a run; all captured for x = graph_x
-  std::map<std::pair<int, int64_t>, hipGraphExec_t> graphs;
+  cgx::GraphCache graphs;  // captured iterations, all for x = graph_x
   void *graph_x = nullptr;
   // cgx_cg_run's two poll events, created once (an event create and destroy
   // per run sat inside every caller's timed region)
@@ -284,9 +297,9 @@ struct cgx_cg {
     int64_t ldb = 0, ldx = 0;
     int slot = 0;
     bool begun = false;
-    // captured chunks keyed by (first slot, bodies), for X = graph_x at
-    // leading dimension graph_ldx and width graph_w
-    std::map<std::pair<int, int64_t>, hipGraphExec_t> graphs;
+    // captured chunks, for X = graph_x at leading dimension graph_ldx and
+    // width graph_w
+    cgx::GraphCache graphs;
     void *graph_x = nullptr;
     int64_t graph_ldx = 0;
     int graph_w = 0;
