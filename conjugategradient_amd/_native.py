@@ -27,6 +27,8 @@ _AB_BUILD = False
 HEADER = os.path.join(os.path.dirname(HERE), "include", "cgx.h")
 
 F64, F32 = 0, 1
+# cgx_many_set_form's forms (cgx.h)
+MANY_FORM_AUTO, MANY_FORM_WORKGROUP, MANY_FORM_WAVE = 0, 1, 2
 
 
 class CgxError(RuntimeError):
@@ -139,6 +141,8 @@ _SIGS = {
     "cgx_many_set_precond": (_i32, [_vp, _i32, _vp, _i64]),
     "cgx_many_get_precond": (_i32, [_vp, C.POINTER(_i32)]),
     "cgx_many_rz": (_i32, [_vp, C.POINTER(_dbl)]),
+    "cgx_many_set_form": (_i32, [_vp, _i32]),
+    "cgx_many_get_form": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "cgx_accuracy": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_dbl)]),
     "cgx_poisson_nnz": (_i64, [_i32, _i32, _i32, _i32, _i64, _i64]),
     "cgx_poisson_fill": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),

@@ -692,9 +692,13 @@ class ManyCG:
     does not fit, n outside 1..4096 or a malformed ``rows``. ``set_values``
     overwrites the values in place for the next solve (no new create).
     ``set_preconditioner`` turns on Jacobi or a caller's diagonal inside the
-    kernel (cgx_many_set_precond); ``rz`` then holds each system's final r.z."""
+    kernel (cgx_many_set_precond); ``rz`` then holds each system's final r.z.
+    ``set_form`` chooses between a workgroup and, for n <= 256, a wave per
+    system (cgx_many_set_form); ``form`` is (requested, in effect)."""
 
     MAX_N = 4096
+    FORM_AUTO, FORM_WORKGROUP, FORM_WAVE = (N.MANY_FORM_AUTO, N.MANY_FORM_WORKGROUP,
+                                            N.MANY_FORM_WAVE)
 
     def __init__(self, queue: Queue, rows, cols, vals, max_workgroups: int = 0):
         vals = np.asarray(vals)
@@ -742,6 +746,24 @@ class ManyCG:
         wg, r, lds = C.c_int(0), C.c_int(0), C.c_int64(0)
         check(lib().cgx_many_info(self._h, C.byref(wg), C.byref(r), C.byref(lds)))
         return wg.value, r.value, lds.value
+
+    def set_form(self, form) -> None:
+        """The next solves' kernel form: ``FORM_AUTO`` (the default),
+        ``FORM_WORKGROUP`` (a workgroup per system) or ``FORM_WAVE`` (a wave per
+        system, n <= 256; CgxError above). The results do not depend on it
+        wherever the dots are clear, and not at all for n <= 64. ValueError,
+        before any device call, for an unknown form."""
+        if form not in (self.FORM_AUTO, self.FORM_WORKGROUP, self.FORM_WAVE) or \
+                isinstance(form, (bool, float)):
+            raise ValueError(f"unknown form {form!r}")
+        check(lib().cgx_many_set_form(self._h, int(form)))
+
+    @property
+    def form(self):
+        """(the form as requested, the form the next solve launches: 1 or 2)"""
+        req, eff = C.c_int(0), C.c_int(0)
+        check(lib().cgx_many_get_form(self._h, C.byref(req), C.byref(eff)))
+        return req.value, eff.value
 
     def set_values(self, vals) -> None:
         """Overwrite every system's values in place; the next solve reads them."""

@@ -13,7 +13,9 @@
 // ascending entry order, the dots double-length sums (cgx_dd.h) rounded once,
 // stop rule Q5 as k_update_xp applies it. With cgx_many_set_precond the same
 // kernel runs PCG with a diagonal M^-1 (k_many_cg's PC), pinned the same way
-// to mode 1 under cgx_cg_set_precond.
+// to mode 1 under cgx_cg_set_precond. For n <= 256 k_many_cg_wave gives each
+// system a wave instead (cgx_many_set_form): the same arithmetic, four
+// independent solves per workgroup and no workgroup barrier.
 #include <cmath>
 #include <climits>
 #include <limits>
@@ -303,6 +305,224 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
   }
 }
 
+// ---- a wave per system (n <= 256; cgx_many_set_form) --------
+constexpr int kWave = 64;
+constexpr int kWaves = kBlock / kWave;  // systems a workgroup runs side by side
+constexpr int kManyWaveMaxN = 4 * kWave;  // rows of one system in the wave form
+
+// Orders a wave's LDS accesses around it: what the lanes wrote before is what
+// they read after, and nothing read before is overwritten early. A wave issues
+// its LDS instructions in order, so all this has to stop is the compiler: a
+// wavefront-scope fence and a wave barrier, neither of which is an s_barrier.
+__device__ __forceinline__ void wave_order() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// lane 0's value in every lane, as scalars: the compiler sees it wave-uniform
+__device__ __forceinline__ double wave_first(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// The wave's sum of one pair per lane, rounded once, the same bits in every
+// lane. At R = 1 it is many_sum's value: the workgroup form's waves 1 to 3
+// then add Dd(0, 0), which changes neither hi nor the rounded value.
+__device__ __forceinline__ double wave_dot(Dd<double> v) {
+  return wave_first(wave_sum_dd(v).value());
+}
+
+// R rows per lane: n <= R kWave. Wave w of workgroup b runs systems 4 b + w,
+// 4 b + w + 4 grid, ...; lane l owns rows l, l + 64, ...: their x and r in
+// registers, p (and m under PC) in the wave's own R kWave doubles of LDS. The
+// four waves of a workgroup never meet: there is no workgroup barrier below
+// (they run different body counts, so one would hang), only wave_order()
+// where k_many_cg has a barrier. The arithmetic is k_many_cg's, statement for
+// statement; a bad diagonal's verdict is a wave vote.
+template <int R, bool PC>
+__global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
+  __shared__ double p_all[kWaves * R * kWave];
+  __shared__ double m_all[PC ? kWaves * R * kWave : 1];  // (unused, and dropped, without PC)
+  const int lane = threadIdx.x & (kWave - 1), n = a.n;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  double *const p = p_all + w * (R * kWave);
+  [[maybe_unused]] double *const mm = m_all + (PC ? w * (R * kWave) : 0);
+  // the pattern is every system's: a lane's row bounds stay in registers
+  int e0[R], e1[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    const int i = lane + k * kWave;
+    e0[k] = i < n ? a.rowptr[i] : 0;
+    e1[k] = i < n ? a.rowptr[i + 1] : 0;
+  }
+  for (int s = blockIdx.x * kWaves + w; s < a.nsys; s += gridDim.x * kWaves) {
+    const double *__restrict__ val = a.val + (int64_t)s * a.ldv;
+    const double *__restrict__ b = a.B + (int64_t)s * a.ldb;
+    double *__restrict__ xs = a.X + (int64_t)s * a.ldx;
+    double x[R], r[R];
+    // ---- init: r = b - A x, p = r, rxr = r.r (k_cg_init) ----
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = lane + k * kWave;
+      x[k] = i < n ? xs[i] : 0.0;
+      if (i < n) p[i] = x[k];  // x through LDS: the init's gather source
+    }
+    if constexpr (PC) {  // m of the own rows, and the verdict on it
+      bool bad = false;
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = lane + k * kWave;
+        if (i < n) {
+          double mv;
+          if (a.M) {
+            mv = a.M[(int64_t)s * a.ldm + i];
+            bad = bad || !many_pc_ok(mv);
+          } else {
+            double d = 0.0;
+            bool found = false;
+            for (int e = e0[k]; e < e1[k]; ++e)
+              if (a.col[e] == i) {
+                d = d + val[e];
+                found = true;
+              }
+            mv = 1.0 / d;
+            bad = bad || !found || !many_pc_ok(d);
+          }
+          mm[i] = mv;
+        }
+      }
+      if (__any(bad)) {  // uniform: the wave's vote
+        if (lane == 0) {
+          a.bodies[s] = 0;
+          a.rxr[s] = __builtin_nan("");
+          a.rz[s] = __builtin_nan("");
+          a.stopped[s] = 3;
+        }
+        continue;  // (p holds x, which nobody gathered: the next system overwrites it)
+      }
+    }
+    wave_order();  // x is in p
+    Dd<double> acc(0.0);
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = lane + k * kWave;
+      double sum = 0.0;
+      for (int e = e0[k]; e < e1[k]; ++e) sum = sum + val[e] * p[a.col[e]];
+      r[k] = 0.0;
+      if (i < n) {
+        r[k] = b[i] - sum;
+        acc += r[k] * r[k];
+      }
+    }
+    wave_order();  // every gather of x is done: p may be overwritten
+    double rxr, rz = 0.0;
+    if constexpr (PC) {  // p = m o r, rz = r.(m o r) (k_pc_init)
+      Dd<double> accz(0.0);
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = lane + k * kWave;
+        if (i < n) {
+          const double z = mm[i] * r[k];
+          p[i] = z;
+          accz += r[k] * z;
+        }
+      }
+      rxr = wave_dot(acc);
+      rz = wave_dot(accz);
+    } else {
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = lane + k * kWave;
+        if (i < n) p[i] = r[k];
+      }
+      rxr = wave_dot(acc);
+    }
+    wave_order();  // p is written
+    long long bodies = 0;
+    int stopped = 0;
+    // ---- the bodies ----
+    for (;;) {
+      // Ap = A p and p.Ap (k_spmv_dot)
+      double Ap[R];
+      acc = Dd<double>(0.0);
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = lane + k * kWave;
+        double sum = 0.0;
+        for (int e = e0[k]; e < e1[k]; ++e) sum = sum + val[e] * p[a.col[e]];
+        Ap[k] = sum;
+        if (i < n) acc += sum * p[i];
+      }
+      const double pAp = wave_dot(acc);
+      const double alpha = (PC ? rz : rxr) / pAp;
+      // r -= alpha Ap and r.r (k_update_r); PC: r.z in the same sweep, z
+      // kept where Ap was (update_r_pc_body)
+      acc = Dd<double>(0.0);
+      double rr, rzn = 0.0;
+      if constexpr (PC) {
+        Dd<double> accz(0.0);
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+          const int i = lane + k * kWave;
+          if (i < n) {
+            r[k] = r[k] - alpha * Ap[k];
+            acc += r[k] * r[k];
+            const double z = mm[i] * r[k];
+            accz += r[k] * z;
+            Ap[k] = z;
+          }
+        }
+        rr = wave_dot(acc);
+        rzn = wave_dot(accz);
+      } else {
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+          const int i = lane + k * kWave;
+          if (i < n) {
+            r[k] = r[k] - alpha * Ap[k];
+            acc += r[k] * r[k];
+          }
+        }
+        rr = wave_dot(acc);
+      }
+      const double beta = PC ? rzn / rz : rr / rxr;
+      wave_order();  // every gather of this body's p is done
+      // x += alpha p; p = r + beta p (PC: m o r + beta p); the stop rule
+      // (k_update_xp, k_update_xp_pc)
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = lane + k * kWave;
+        if (i < n) {
+          const double pv = p[i];
+          x[k] = x[k] + alpha * pv;
+          p[i] = (PC ? Ap[k] : r[k]) + beta * pv;
+        }
+      }
+      ++bodies;
+      const bool cond = isnan(rxr) || sqrt(rxr) <= a.tol;  // Q5: the r.r the body began with
+      const bool cont = !cond && bodies < a.cap;
+      stopped = cond ? 1 : (cont ? 0 : 2);
+      rxr = rr;
+      if constexpr (PC) rz = rzn;
+      wave_order();  // the new p, before the next gather (or the next system's x)
+      if (!cont) break;
+    }
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = lane + k * kWave;
+      if (i < n) xs[i] = x[k];
+    }
+    if (lane == 0) {
+      a.bodies[s] = bodies;
+      a.rxr[s] = rxr;
+      a.stopped[s] = stopped;
+      if constexpr (PC) a.rz[s] = rz;
+    }
+  }
+}
+
 // The pattern's check, once at create: bad[0] counts the entries of rowptr
 // that are outside [0, nnz], descend, or miss rowptr[0] = 0 / rowptr[n] = nnz,
 // bad[1] the columns outside [0, n).
@@ -344,23 +564,40 @@ template <bool PC> const void *many_kernel_of(int r) {
   }
 }
 
-const void *many_kernel(int r, bool pc) {
+int many_rows_per_lane(int64_t n) {  // the wave form's R (n <= kManyWaveMaxN)
+  int r = 1;
+  while ((int64_t)r * kWave < n) r *= 2;
+  return r;
+}
+
+template <bool PC> const void *many_wave_kernel_of(int r) {
+  switch (r) {
+    case 1: return reinterpret_cast<const void *>(&k_many_cg_wave<1, PC>);
+    case 2: return reinterpret_cast<const void *>(&k_many_cg_wave<2, PC>);
+    case 4: return reinterpret_cast<const void *>(&k_many_cg_wave<4, PC>);
+    default: return nullptr;
+  }
+}
+
+const void *many_kernel(int r, bool pc, bool wave) {
+  if (wave) return pc ? many_wave_kernel_of<true>(r) : many_wave_kernel_of<false>(r);
   return pc ? many_kernel_of<true>(r) : many_kernel_of<false>(r);
 }
 
-// workgroups of k_many_cg<r, pc> resident on the device at once (occupancy x
-// CUs; 0: unknown), as spmv_dot_resident
-int many_resident(int r, bool pc) {
+// workgroups of k_many_cg<r, pc> (wave: k_many_cg_wave<r, pc>) resident on the
+// device at once (occupancy x CUs; 0: unknown), as spmv_dot_resident
+int many_resident(int r, bool pc, bool wave) {
   static std::mutex mu;
-  static std::map<std::pair<int, int>, int> cache;  // (device, r or -r with pc) -> workgroups
+  // (device, 4 r + 2 with the wave form + 1 with pc) -> workgroups
+  static std::map<std::pair<int, int>, int> cache;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   std::lock_guard<std::mutex> lk(mu);
-  const std::pair<int, int> key{dev, pc ? -r : r};
+  const std::pair<int, int> key{dev, 4 * r + (wave ? 2 : 0) + (pc ? 1 : 0)};
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
   int res = 0, nb = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, many_kernel(r, pc), kBlock, 0) ==
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, many_kernel(r, pc, wave), kBlock, 0) ==
           hipSuccess &&
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
     res = nb * cus;
@@ -375,7 +612,8 @@ struct cgx_many {
   int64_t nsys = 0, n = 0, nnz = 0, ldv = 0;
   const int *rowptr = nullptr, *col = nullptr;  // the caller's
   const double *val = nullptr;
-  int r = 1;               // rows per thread
+  int r = 1;               // rows per thread (the workgroup form's)
+  int form = CGX_MANY_FORM_AUTO;  // cgx_many_set_form: as requested
   int max_workgroups = 0;  // cgx_many_config (0: the resident workgroups)
   int precond = CGX_PRECOND_NONE;  // cgx_many_set_precond: the next solve's
   const double *d_M = nullptr;     // DIAGONAL: the caller's
@@ -414,9 +652,34 @@ void many_launch(int r, dim3 grid, dim3 block, hipStream_t s, const ManyArgs &a)
   }
 }
 
+template <bool PC>
+void many_launch_wave(int r, dim3 grid, dim3 block, hipStream_t s, const ManyArgs &a) {
+  switch (r) {
+    case 1: hipLaunchKernelGGL((k_many_cg_wave<1, PC>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((k_many_cg_wave<2, PC>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((k_many_cg_wave<4, PC>), grid, block, 0, s, a); break;
+  }
+}
+
+// Auto takes the wave form up to this many rows (0: never). See DESIGN.md §5e,
+// "A wave per system", for the measurement behind the value.
+constexpr int kManyAutoWaveMaxN = 64;
+
+// the form the next solve launches: CGX_MANY_FORM_WORKGROUP or CGX_MANY_FORM_WAVE
+int many_form(const cgx_many *m) {
+  if (m->form != CGX_MANY_FORM_AUTO) return m->form;
+  return m->n <= kManyAutoWaveMaxN ? CGX_MANY_FORM_WAVE : CGX_MANY_FORM_WORKGROUP;
+}
+
+// rows per thread (per lane in the wave form) of the next solve's instantiation
+int many_rows(const cgx_many *m) {
+  return many_form(m) == CGX_MANY_FORM_WAVE ? many_rows_per_lane(m->n) : m->r;
+}
+
 int many_grid(const cgx_many *m) {
-  int64_t g = m->nsys;
-  const int res = many_resident(m->r, m->precond != CGX_PRECOND_NONE);
+  const bool wave = many_form(m) == CGX_MANY_FORM_WAVE;
+  int64_t g = wave ? (m->nsys + kWaves - 1) / kWaves : m->nsys;
+  const int res = many_resident(many_rows(m), m->precond != CGX_PRECOND_NONE, wave);
   if (res > 0) g = std::min<int64_t>(g, res);
   if (m->max_workgroups > 0) g = std::min<int64_t>(g, m->max_workgroups);
   return (int)std::min<int64_t>(std::max<int64_t>(g, 1), INT_MAX);
@@ -568,8 +831,13 @@ extern "C" int cgx_many_solve(cgx_many *m, const void *d_B, int64_t ldb, void *d
   a.rz = m->d_rz;
   m->rz_valid = false;
   const dim3 grid(many_grid(m)), block(kBlock);
-  if (pc) many_launch<true>(m->r, grid, block, s, a);
-  else many_launch<false>(m->r, grid, block, s, a);
+  if (many_form(m) == CGX_MANY_FORM_WAVE) {
+    if (pc) many_launch_wave<true>(many_rows(m), grid, block, s, a);
+    else many_launch_wave<false>(many_rows(m), grid, block, s, a);
+  } else {
+    if (pc) many_launch<true>(m->r, grid, block, s, a);
+    else many_launch<false>(m->r, grid, block, s, a);
+  }
   CGX_HIP(hipGetLastError());
   const size_t ns = (size_t)m->nsys;
   if (pc) CGX_HIP(hipMemcpyAsync(m->h_rz, m->d_rz, ns * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -627,10 +895,35 @@ extern "C" int cgx_many_info(cgx_many *m, int *workgroups, int *rows_per_thread,
   CGX_REQUIRE(m, CGX_EINVAL, "NULL argument");
   DeviceGuard g(m->ctx->device);
   if (workgroups) *workgroups = many_grid(m);
-  if (rows_per_thread) *rows_per_thread = m->r;
-  if (lds_bytes)  // p and the stagings; preconditioned: m, wider stagings and the verdict word
-    *lds_bytes = m->precond == CGX_PRECOND_NONE
-                     ? ((int64_t)m->r * kBlock + 16) * (int64_t)sizeof(double)
-                     : ((int64_t)2 * m->r * kBlock + 32) * (int64_t)sizeof(double) + 8;
+  if (rows_per_thread) *rows_per_thread = many_rows(m);
+  if (lds_bytes) {
+    if (many_form(m) == CGX_MANY_FORM_WAVE)  // four waves' p; preconditioned: their m too
+      *lds_bytes = (int64_t)(m->precond == CGX_PRECOND_NONE ? 1 : 2) * kWaves * many_rows(m) *
+                   kWave * (int64_t)sizeof(double);
+    else  // p and the stagings; preconditioned: m, wider stagings and the verdict word
+      *lds_bytes = m->precond == CGX_PRECOND_NONE
+                       ? ((int64_t)m->r * kBlock + 16) * (int64_t)sizeof(double)
+                       : ((int64_t)2 * m->r * kBlock + 32) * (int64_t)sizeof(double) + 8;
+  }
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_set_form(cgx_many *m, int form) {
+  CGX_REQUIRE(form == CGX_MANY_FORM_AUTO || form == CGX_MANY_FORM_WORKGROUP ||
+                  form == CGX_MANY_FORM_WAVE,
+              CGX_EINVAL, "cgx_many_set_form: unknown form %d", form);
+  CGX_REQUIRE(m, CGX_EINVAL, "cgx_many_set_form: NULL handle");
+  CGX_REQUIRE(form != CGX_MANY_FORM_WAVE || m->n <= kManyWaveMaxN, CGX_EUNSUPPORTED,
+              "cgx_many_set_form: n %lld exceeds %d rows, the most one wave holds; larger "
+              "systems run in the workgroup form",
+              (long long)m->n, kManyWaveMaxN);
+  m->form = form;
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_get_form(cgx_many *m, int *requested, int *in_effect) {
+  CGX_REQUIRE(m, CGX_EINVAL, "cgx_many_get_form: NULL handle");
+  if (requested) *requested = m->form;
+  if (in_effect) *in_effect = many_form(m);
   return CGX_OK;
 }

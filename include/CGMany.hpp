@@ -104,6 +104,26 @@ template <typename DT> class CGMany {
   int preconditioner() const { return _precond; }
 
   /**
+   * The next solves' kernel form (cgx_many_set_form): CGX_MANY_FORM_AUTO (the
+   * default), CGX_MANY_FORM_WORKGROUP or CGX_MANY_FORM_WAVE, a wave per system
+   * for n <= 256.
+   * @throw std::invalid_argument for an unknown form; std::runtime_error from
+   *        the library for the wave form above 256 rows
+   */
+  void setForm(int form) {
+    if (form != CGX_MANY_FORM_AUTO && form != CGX_MANY_FORM_WORKGROUP &&
+        form != CGX_MANY_FORM_WAVE)
+      throw std::invalid_argument("CGMany::setForm: unknown form");
+    check(cgx_many_set_form(_many.get(), form), "cgx_many_set_form");
+  }
+  /** the form the next solve launches: CGX_MANY_FORM_WORKGROUP or CGX_MANY_FORM_WAVE */
+  int form() const {
+    int in_effect = 0;
+    check(cgx_many_get_form(_many.get(), nullptr, &in_effect), "cgx_many_get_form");
+    return in_effect;
+  }
+
+  /**
    * B and X: nsys * n host values, system-major; X holds the initial guesses
    * and receives the results. improvement: the absolute tolerance on sqrt(r.r).
    * @throw std::invalid_argument for a wrong length

@@ -501,8 +501,9 @@ int cgx_mixed_inner(cgx_mixed *m, cgx_csr **A32, cgx_cg **cg32);
  * its allocated size, as of the call. Replaces nothing in the reference. */
 int cgx_mixed_bytes(cgx_mixed *m, int64_t *bytes);
 
-/* ---- cgx_many: many small systems, one workgroup per system (replaces
- * nothing in the reference, which solves one system) ----------
+/* ---- cgx_many: many small systems, one workgroup (or, up to 256 rows, one
+ * wave: cgx_many_set_form) per system (replaces nothing in the reference,
+ * which solves one system) ----------
  * nsys SPD systems of n <= 4,096 rows share one sparsity pattern (d_rowptr:
  * n + 1 entries, d_col: nnz entries, entries in CSR order as given); system s
  * has its own values at d_val + s * ldv, its right-hand side at d_B + s * ldb
@@ -527,10 +528,10 @@ int cgx_mixed_bytes(cgx_mixed *m, int64_t *bytes);
  * assembly; irregular_spd(1000) 6.36 against 2,974 and 37.9.
  * Diagonal preconditioning (cgx_many_set_precond) runs in the same kernel: see
  * there.
- * Out of scope: f32 systems, a preconditioner other than a diagonal, a
- * wave-per-system form for n <= 64, systems with differing patterns,
- * partitioned or multi-GPU use, and any auto route from cgx_cg_solve into this
- * path. */
+ * Out of scope: f32 systems, a preconditioner other than a diagonal, systems
+ * with differing patterns, partitioned or multi-GPU use, and any auto route
+ * from cgx_cg_solve into this path; in the wave form (cgx_many_set_form) also
+ * several systems per wave for n <= 32 and values cached in registers. */
 typedef struct cgx_many cgx_many;
 /* dtype: CGX_F64 (CGX_F32: CGX_EUNSUPPORTED). 1 <= n <= 4,096 (above:
  * CGX_EUNSUPPORTED; use cgx_cg_solve), nsys >= 1, ldv >= nnz, rows of any
@@ -548,7 +549,8 @@ int cgx_many_create(cgx_ctx *ctx, int dtype, int64_t nsys, int64_t n, int64_t nn
 /* Replaces nothing in the reference. */
 int cgx_many_destroy(cgx_many *m);
 /* max_workgroups caps the grid, min(nsys, resident workgroups,
- * max_workgroups); 0: no cap (the default), negative: CGX_EINVAL. A tuning
+ * max_workgroups) (in the wave form ceil(nsys / 4) takes the place of nsys:
+ * cgx_many_set_form); 0: no cap (the default), negative: CGX_EINVAL. A tuning
  * knob, as cgx_cg_config: a workgroup takes systems blockIdx, blockIdx + grid,
  * ... and the results do not depend on it. Replaces nothing in the reference. */
 int cgx_many_config(cgx_many *m, int max_workgroups);
@@ -562,9 +564,11 @@ int cgx_many_config(cgx_many *m, int max_workgroups);
 int cgx_many_solve(cgx_many *m, const void *d_B, int64_t ldb, void *d_X, int64_t ldx, double tol,
                    int64_t max_bodies, int64_t *bodies_out, double *rxr_out, int *stopped_out);
 /* *workgroups: the grid the next solve launches; *rows_per_thread: the
- * instantiation (1, 2, 4, 8 or 16: the least with n <= 256 rows_per_thread);
- * *lds_bytes: its LDS per workgroup. Each may be NULL.
- * Replaces nothing in the reference. */
+ * instantiation (1, 2, 4, 8 or 16: the least with n <= 256 rows_per_thread;
+ * in the wave form 1, 2 or 4 rows per lane: the least with n <= 64
+ * rows_per_thread); *lds_bytes: its LDS per workgroup (wave form: four waves'
+ * p, 4 * 64 rows_per_thread doubles, twice that under a preconditioner). Each
+ * may be NULL. Replaces nothing in the reference. */
 int cgx_many_info(cgx_many *m, int *workgroups, int *rows_per_thread, int64_t *lds_bytes);
 /* Diagonal preconditioning inside the many-systems kernel. kind: CGX_PRECOND_NONE
  * (the default), CGX_PRECOND_JACOBI or CGX_PRECOND_DIAGONAL; it may be set
@@ -602,6 +606,41 @@ int cgx_many_get_precond(cgx_many *m, int *kind);
  * CGX_ESTATE without a preconditioner, or before a solve under the one that
  * is set. Replaces nothing in the reference. */
 int cgx_many_rz(cgx_many *m, double *rz_out);
+
+/* The form of the many-systems kernel. WORKGROUP: one workgroup of 256 threads
+ * per system, any n <= 4,096 (above). WAVE: one wave per system for n <= 256:
+ * wave w of workgroup g runs systems 4 g + w, 4 g + w + 4 grid, ...; lane l
+ * owns rows l, l + 64, ... (1, 2 or 4 rows per lane), their x and r in
+ * registers, p (and m under a preconditioner) in LDS of the wave's own; a dot
+ * is a wave reduction broadcast from lane 0, a bad diagonal's verdict a wave
+ * vote. The four waves of a workgroup run four independent solves and never
+ * wait for each other: the kernel has no workgroup barrier. The grid is
+ * min(ceil(nsys / 4), resident workgroups, max_workgroups); results do not
+ * depend on it. AUTO (the default) takes the wave form for n <= 64 and the
+ * workgroup form above; for 65 <= n <= 256 the wave form is by request only.
+ * Arithmetic (normative): the workgroup form's, statement for statement, with
+ * the same pin to cgx_cg_solve in mode 1 (with cgx_cg_set_precond under a
+ * preconditioner) wherever the dots are clear, and the same outputs for a bad
+ * diagonal (X untouched, 0 bodies, NaN r.r and r.z, stop code 3). For n <= 64
+ * the two forms give the same bits, clear or not, NaN and Inf included: the
+ * workgroup form's other three waves add (0, 0) to the double-length sum.
+ * Measured with tools/many_wave_bench.py on an MI355X (65,536 systems to 1e-8
+ * ||b||, medians; profiles/many_wave_bench.log), µs per system workgroup ->
+ * wave: scaled 8 x 8 Poisson 0.105 -> 0.026 (JACOBI 0.119 -> 0.027),
+ * irregular_spd(60) 0.212 -> 0.080 (0.168 -> 0.047); by request at n = 121
+ * 0.145 -> 0.049 and at n = 256 0.225 -> 0.156. Every wave round lay below
+ * every workgroup round, which is why AUTO takes the wave form up to 64 rows.
+ * cgx_many_set_form: CGX_EINVAL, before any device call, for an unknown form
+ * or a NULL handle; CGX_EUNSUPPORTED for WAVE on an object with n > 256 (use
+ * the workgroup form). It may be called between solves and takes effect at
+ * the next one (cgx_many_info then reports that form's instantiation); on an
+ * error the object keeps the form it had.
+ * cgx_many_get_form: *requested as set, *in_effect CGX_MANY_FORM_WORKGROUP or
+ * CGX_MANY_FORM_WAVE: what the next solve launches. Each may be NULL.
+ * Replace nothing in the reference. */
+enum { CGX_MANY_FORM_AUTO = 0, CGX_MANY_FORM_WORKGROUP = 1, CGX_MANY_FORM_WAVE = 2 };
+int cgx_many_set_form(cgx_many *m, int form);
+int cgx_many_get_form(cgx_many *m, int *requested, int *in_effect);
 
 /* CG::accuracy (CG.hpp:463-515): blocking; |sum (b-Ax)^2 / sum x^2|. */
 int cgx_accuracy(cgx_ctx *ctx, cgx_csr *A, const void *d_b, const void *d_x,
