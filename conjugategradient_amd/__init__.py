@@ -10,11 +10,11 @@ behind the interfaces of XeniaHerr/ConjugateGradient:
 """
 from ._native import (MANY_FORM_AUTO, MANY_FORM_WAVE, MANY_FORM_WORKGROUP,  # noqa: F401
                       CgxError, device_count, header_symbols, lib)
-from .core import (CG, DeviceArray, Debuglevel, Event, ManyCG, Matrix,  # noqa: F401
-                   Preconditioner, Queue, Scalar, Vector, VectorOperations)
+from .core import (CG, BlockPreconditioner, DeviceArray, Debuglevel, Event,  # noqa: F401
+                   ManyCG, Matrix, Preconditioner, Queue, Scalar, Vector, VectorOperations)
 from .mtx import read_file, write_mtx_lower  # noqa: F401
 
-__all__ = ["CG", "CgxError", "Debuglevel", "DeviceArray", "Event", "MANY_FORM_AUTO",
-           "MANY_FORM_WAVE", "MANY_FORM_WORKGROUP", "ManyCG", "Matrix", "Preconditioner", "Queue",
-           "Scalar", "Vector", "VectorOperations", "device_count", "header_symbols", "lib",
+__all__ = ["BlockPreconditioner", "CG", "CgxError", "Debuglevel", "DeviceArray", "Event",
+           "MANY_FORM_AUTO", "MANY_FORM_WAVE", "MANY_FORM_WORKGROUP", "ManyCG", "Matrix",
+           "Preconditioner", "Queue", "Scalar", "Vector", "VectorOperations", "device_count", "header_symbols", "lib",
            "read_file", "write_mtx_lower"]

@@ -115,6 +115,9 @@ _SIGS = {
     "cgx_cg_set_precond": (_i32, [_vp, _i32, _vp]),
     "cgx_cg_get_precond": (_i32, [_vp, C.POINTER(_i32)]),
     "cgx_cg_rz": (_i32, [_vp, C.POINTER(_dbl)]),
+    "cgx_csr_block_inv": (_i32, [_vp, _i32, _vp]),
+    "cgx_cg_set_block_precond": (_i32, [_vp, _i32, _i32, _vp]),
+    "cgx_cg_get_block_precond": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "cgx_cg_solve_batch": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _dbl, _i64, C.POINTER(_i64),
                                   C.POINTER(_dbl), C.POINTER(_i32)]),
     "cgx_cg_begin_batch": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _dbl, _i64]),

@@ -34,6 +34,17 @@ class Preconditioner(enum.IntEnum):
     Diagonal = 2   # a positive vector the caller supplies
 
 
+class BlockPreconditioner(enum.IntEnum):
+    """Extension (cgx.h CGX_BLOCK_*): block-Jacobi preconditioning of CG.solve
+    with dense diagonal blocks of 1 to 8 rows."""
+    None_ = 0
+    Jacobi = 1     # the inverses of A's diagonal blocks, built on the device
+    Given = 2      # an (n, block_size) array of blocks the caller supplies
+
+
+MAX_BLOCK_SIZE = 8
+
+
 def _dtype_code(dtype) -> int:
     dt = np.dtype(dtype)
     if dt == np.float64:
@@ -186,6 +197,20 @@ class Matrix:
         out = DeviceArray(self._queue, self._N, self.dtype)
         check(lib().cgx_csr_diag_inv(self.schedule(), out.ptr))
         return out.download()
+
+    def block_inv(self, block_size: int) -> np.ndarray:
+        """Extension: the inverses of the diagonal blocks of ``block_size``
+        rows (1..8) as an (N, block_size) array, row i holding its row of its
+        block's inverse (cgx_csr_block_inv; the columns past a partial last
+        block are 0) — block-Jacobi's W. ValueError for a block size outside
+        1..8, before any device call; CgxError when a block has a pivot that is
+        not positive and finite."""
+        bs = int(block_size)
+        if not 1 <= bs <= MAX_BLOCK_SIZE:
+            raise ValueError(f"block_size {block_size!r} must be 1..{MAX_BLOCK_SIZE}")
+        out = DeviceArray(self._queue, max(self._N * bs, 1), self.dtype)
+        check(lib().cgx_csr_block_inv(self.schedule(), bs, out.ptr))
+        return out.download()[:self._N * bs].reshape(self._N, bs)
 
     def data(self):
         return self._data
@@ -375,6 +400,9 @@ class CG:
         self.final_rz = float("nan")   # extension: r.z after the last body (preconditioned)
         self._precond = Preconditioner.None_
         self._minv = None  # the caller's diagonal (a Vector), kept alive for the solver
+        self._blk = BlockPreconditioner.None_  # setBlockPreconditioner: kind, block size and
+        self._blk_bs = 0                       # the caller's blocks (host; the solver copies)
+        self._blk_w = None
         self.poll_every = 32
         self.use_graph = True
         self.mode = 0  # cgx_cg_set_mode: 0 auto (5, 4, 6 or 3), 1 three kernels, 2 fused,
@@ -457,10 +485,60 @@ class CG:
             minv = diag if isinstance(diag, Vector) else Vector(self._queue, np.asarray(diag),
                                                                 dtype=self.dtype)
         self._precond, self._minv = kind, minv
+        self._blk, self._blk_bs, self._blk_w = BlockPreconditioner.None_, 0, None  # replaced
+        if self._cg is not None and self._cg_for == self.A._csr:
+            self._apply_precond()
+
+    def setBlockPreconditioner(self, kind, block_size: int = 0, blocks=None) -> None:
+        """Extension: block-Jacobi preconditioning of the following solves
+        (cgx_cg_set_block_precond; float64, modes 1 and 3, auto resolves to 3;
+        the stop rule still tests the true r.r). ``Jacobi`` inverts A's
+        diagonal blocks of ``block_size`` rows (1..8) on the device, from the
+        matrix in place at each solve; ``Given`` takes ``blocks``, an
+        (N, block_size) array whose row i is row i of its block's matrix — each
+        block symmetric positive definite, which is the caller's duty (only
+        finite entries and a positive diagonal are checked). It replaces a
+        preconditioner set by ``setPreconditioner`` and is replaced by it.
+        ValueError, before any device call, for an unknown kind, a block size
+        outside 1..8, missing ``blocks`` or a wrong shape; TypeError on a
+        float32 CG."""
+        try:
+            kind = BlockPreconditioner(kind)
+        except (ValueError, TypeError):
+            raise ValueError(f"unknown block preconditioner kind {kind!r}") from None
+        bs, w = 0, None
+        if kind != BlockPreconditioner.None_:
+            if self.dtype != np.float64:
+                raise TypeError(f"block preconditioning is float64; this CG is {self.dtype}")
+            bs = int(block_size)
+            if not 1 <= bs <= MAX_BLOCK_SIZE:
+                raise ValueError(f"block_size {block_size!r} must be 1..{MAX_BLOCK_SIZE}")
+        if kind == BlockPreconditioner.Given:
+            if blocks is None:
+                raise ValueError("BlockPreconditioner.Given needs blocks")
+            arr = np.ascontiguousarray(blocks, dtype=np.float64)
+            if arr.ndim != 2 or arr.shape[1] != bs or arr.shape[0] == 0:
+                raise ValueError(f"blocks has shape {arr.shape}, expected (N, {bs})")
+            if self.A.N() and arr.shape[0] != self.A.N():
+                raise ValueError(f"blocks has {arr.shape[0]} rows, the matrix {self.A.N()}")
+            w = arr
+        self._blk, self._blk_bs, self._blk_w = kind, bs, w
+        self._precond, self._minv = Preconditioner.None_, None  # replaced
         if self._cg is not None and self._cg_for == self.A._csr:
             self._apply_precond()
 
     def _apply_precond(self) -> None:
+        if self._blk != BlockPreconditioner.None_:
+            d_w = None
+            if self._blk == BlockPreconditioner.Given:
+                if self._blk_w.shape[0] != self.A.N():
+                    raise ValueError(f"blocks has {self._blk_w.shape[0]} rows, the matrix "
+                                     f"{self.A.N()}")
+                d_w = DeviceArray(self._queue, self._blk_w.size, np.float64)
+                d_w.upload(self._blk_w.ravel())  # the solver keeps a copy of its own
+            check(lib().cgx_cg_set_block_precond(self._cg, int(self._blk), self._blk_bs,
+                                                 d_w.ptr if d_w is not None else None))
+            return
         if self._precond == Preconditioner.Diagonal and self._minv.N() != self.A.N():
             raise ValueError(f"diag has {self._minv.N()} entries, the matrix {self.A.N()} rows")
         check(lib().cgx_cg_set_precond(
@@ -484,7 +562,7 @@ class CG:
             self._cg_for = sched
             check(lib().cgx_cg_config(self._cg, self.poll_every, 1 if self.use_graph else 0))
             check(lib().cgx_cg_set_mode(self._cg, self.mode))
-            if self._precond != Preconditioner.None_:
+            if self._precond != Preconditioner.None_ or self._blk != BlockPreconditioner.None_:
                 self._apply_precond()
         return self._cg
 
@@ -505,7 +583,7 @@ class CG:
         self.iterations = bodies.value
         self.final_rxr = rxr.value
         self.final_rz = float("nan")
-        if self._precond != Preconditioner.None_:
+        if self._precond != Preconditioner.None_ or self._blk != BlockPreconditioner.None_:
             rz = C.c_double(0)
             check(lib().cgx_cg_rz(self._cg, C.byref(rz)))
             self.final_rz = rz.value
@@ -561,6 +639,10 @@ class CG:
         m = self._mixed
         inner = _vp()
         check(L.cgx_mixed_inner(m, None, C.byref(inner)))
+        if self._blk != BlockPreconditioner.None_:
+            # refused, whatever the kind: the inner solver is f32 (CGX_EUNSUPPORTED)
+            check(L.cgx_cg_set_block_precond(inner, int(BlockPreconditioner.Jacobi),
+                                             self._blk_bs, None))
         check(L.cgx_cg_config(inner, self.poll_every, 1 if self.use_graph else 0))
         # (mode before the preconditioner, and NONE first: whichever of the two
         # comes second refuses a mode that runs no preconditioner)

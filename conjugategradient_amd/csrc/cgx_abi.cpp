@@ -103,6 +103,12 @@ template <typename T> struct CgView {
         p2((T *)cg->p2), m((const T *)cg->minv) {}
 };
 
+// a preconditioner of either family is set (cgx_cg_set_precond's diagonal or
+// cgx_cg_set_block_precond's blocks: at most one of them at a time)
+bool has_precond(const cgx_cg *cg) {
+  return cg->precond != CGX_PRECOND_NONE || cg->blk_kind != CGX_BLOCK_NONE;
+}
+
 // where rz starts in the solver's CgScalars<T>
 size_t rz_offset(const cgx_cg *cg) {
   return with_dtype(cg->dtype, [](auto t) { return offsetof(CgScalars<decltype(t)>, rz); });
@@ -412,6 +418,25 @@ template <typename T> int enqueue_iter(cgx_cg *cg, const CgView<T> &v, int slot)
   // base + 2)
   const bool pc = cg->precond != CGX_PRECOND_NONE, pc_dist = pc && A->dist;
   int np_rr = sep ? 0 : npr;  // the plain x/p update's r.r partials
+  // block-Jacobi (cgx_cg_set_block_precond; f64, one device, modes 1 and 3):
+  // the plain SpMV launch, update_r with z = M^-1 r stored over Ap, the p
+  // update reading z there
+  if constexpr (std::is_same_v<T, double>) {
+    if (cg->blk_kind != CGX_BLOCK_NONE) {
+      const double *W = (const double *)cg->blk_w;
+      const int bs = cg->blk_bs, npb = blk_update_parts(cg->n, bs);
+      if ((rc = enqueue_spmv_dot<T>(cg, v, p, slot, par, &npp))) return rc;
+      if ((rc = timed(cg, 2, s, [&] {
+             return blk_update_r(cg->n, bs, v.r, v.Ap, W, v.st, slot, v.ws, s, npp, rpar);
+           })))
+        return rc;
+      return timed(cg, 3, s, [&] {
+        if (defer)
+          return blk_update_p_defer(cg->n, v.x, p, pn, v.P, v.Ap, v.st, slot, v.ws, npb, s, par3);
+        return blk_update_xp(cg->n, v.x, p, v.Ap, v.st, slot, v.ws, npb, s, par3);
+      });
+    }
+  }
   if (recomputes_ap(cg->mode)) {
     // mode 6: kernel 1 keeps only p.Ap, kernel 2 forms A p again and updates
     // r in the walk's epilogue (no Ap vector: 8 N bytes written and read
@@ -3211,10 +3236,10 @@ static bool coop_auto(const cgx_cg *cg) {
 // The preconditioner's mode rule: the preconditioned kernels are modes 1 and
 // 3's (a requested mode may also be 0, auto). false, with the error set, for
 // any other mode.
-static bool precond_mode_ok(int mode) {
+static bool precond_mode_ok(int mode, bool block = false) {
   if (mode == 0 || mode == 1 || mode == 3) return true;
-  set_error("mode %d with a preconditioner: diagonal preconditioning runs in modes 1 and 3 "
-            "(auto resolves to 3)", mode);
+  set_error("mode %d with a preconditioner: %s preconditioning runs in modes 1 and 3 "
+            "(auto resolves to 3)", mode, block ? "block" : "diagonal");
   return false;
 }
 
@@ -3225,7 +3250,8 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
               "4 fused with deferred x, 5 persistent body, 6 recomputed Ap, 7 fused with "
               "recomputed Ap", mode);
   const int mode_req = mode;
-  if (cg->precond && !precond_mode_ok(mode)) return CGX_EUNSUPPORTED;
+  if (has_precond(cg) && !precond_mode_ok(mode, cg->blk_kind != CGX_BLOCK_NONE))
+    return CGX_EUNSUPPORTED;
   CGX_REQUIRE(mode != 6 || (!cg->A->dist && vl_whole(cg->A->dev)), CGX_EUNSUPPORTED,
               "mode 6 (recomputed Ap) needs the lean stencil walk on a single device");
   CGX_REQUIRE(mode != 7 || (!cg->A->dist && cg->dtype == CGX_F64 && lean_tile_ok(cg->A->dev)),
@@ -3279,7 +3305,7 @@ extern "C" int cgx_cg_set_mode(cgx_cg *cg, int mode) {
                   (cg->dtype == CGX_F64 && Launch<double>::fd_supported(cg->A->dev)),
               CGX_EUNSUPPORTED, "mode 4 needs an f64 matrix in a production SpMV format "
               "(variant %d has no fused kernel)", launch_variant(cg->A->dev, cg->dtype));
-  if (mode == 0 && cg->precond) {
+  if (mode == 0 && has_precond(cg)) {
     mode = 3;  // the preconditioned kernels are modes 1 and 3's, whatever the matrix
   } else if (mode == 0) {
     mode = coop_auto(cg) ? 5 : fd_auto(cg) ? 4 : 3;
@@ -3541,6 +3567,11 @@ extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
   cg->minv_own = own;
   cg->minv = m;
   cg->precond = kind;
+  // the two families exclude each other: this call replaces a block one
+  if (cg->blk_w) (void)hipFree(cg->blk_w);
+  cg->blk_w = nullptr;
+  cg->blk_kind = CGX_BLOCK_NONE;
+  cg->blk_bs = 0;
   const char *e = std::getenv("CGX_PCG_M_NT");
   cg->minv_nt = e && std::atoi(e) != 0;
   // auto mode depends on the preconditioner (3 with one, the matrix's own without)
@@ -3551,6 +3582,119 @@ extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
 extern "C" int cgx_cg_get_precond(cgx_cg *cg, int *kind) {
   CGX_REQUIRE(cg && kind, CGX_EINVAL, "NULL argument");
   *kind = cg->precond;
+  return CGX_OK;
+}
+
+// ===========================================================================
+// block-Jacobi preconditioning
+// ===========================================================================
+namespace {
+// why block preconditioning cannot run on this matrix (null: it can)
+const char *block_refusal(const cgx_csr *A) {
+  if (A->dist) return "the matrix is partitioned (block preconditioning runs on one device)";
+  if (A->dtype != CGX_F64)
+    return "the matrix is f32 (block preconditioning is f64; cgx_mixed's inner solver is f32)";
+  return nullptr;
+}
+
+// the inverses of A's diagonal blocks into d_out (n * bs doubles); blocking
+int block_inv_impl(cgx_csr *A, int bs, void *d_out) {
+  DeviceGuard g(A->ctx->device);
+  hipStream_t s = A->ctx->stream;
+  unsigned long long h[2] = {0, ~0ull};
+  if (A->dev.n == 0) return CGX_OK;
+  if (int rc = pc_scan(A->ctx, h, [&](unsigned long long *bad) {
+        return blk_inv(A->dev, bs, (double *)d_out, bad, s);
+      }))
+    return rc;
+  CGX_REQUIRE(h[0] == 0, CGX_EINVAL,
+              "cgx_csr_block_inv: %llu block(s) of %d rows with a pivot that is not positive and "
+              "finite; the first is block %llu (first row %llu)",
+              h[0], bs, h[1], h[1] * (unsigned long long)bs);
+  return CGX_OK;
+}
+}  // namespace
+
+extern "C" int cgx_csr_block_inv(cgx_csr *A, int bs, void *d_out) {
+  CGX_REQUIRE(A && d_out, CGX_EINVAL, "NULL argument");
+  CGX_REQUIRE(bs >= 1 && bs <= 8, CGX_EINVAL, "block size %d: 1 to 8", bs);
+  if (const char *why = block_refusal(A)) {
+    set_error("cgx_csr_block_inv: %s", why);
+    return CGX_EUNSUPPORTED;
+  }
+  return block_inv_impl(A, bs, d_out);
+}
+
+extern "C" int cgx_cg_set_block_precond(cgx_cg *cg, int kind, int bs, const void *d_w) {
+  CGX_REQUIRE(cg, CGX_EINVAL, "cg is NULL");
+  CGX_REQUIRE(kind == CGX_BLOCK_NONE || kind == CGX_BLOCK_JACOBI || kind == CGX_BLOCK_GIVEN,
+              CGX_EINVAL, "block preconditioner kind %d: 0 none, 1 block-Jacobi, 2 a caller's "
+              "blocks", kind);
+  void *own = nullptr;
+  if (kind != CGX_BLOCK_NONE) {
+    CGX_REQUIRE(bs >= 1 && bs <= 8, CGX_EINVAL, "block size %d: 1 to 8", bs);
+    CGX_REQUIRE(kind != CGX_BLOCK_GIVEN || d_w, CGX_EINVAL, "CGX_BLOCK_GIVEN needs d_w");
+    CGX_REQUIRE(kind != CGX_BLOCK_GIVEN || ((uintptr_t)d_w & 15) == 0, CGX_EINVAL,
+                "d_w must be 16-byte aligned");
+    if (const char *why = block_refusal(cg->A)) {
+      set_error("cgx_cg_set_block_precond: %s", why);
+      return CGX_EUNSUPPORTED;
+    }
+    CGX_REQUIRE(cg->n > 0, CGX_EUNSUPPORTED, "cgx_cg_set_block_precond: the matrix has no rows");
+    if (!precond_mode_ok(cg->mode_req, true)) return CGX_EUNSUPPORTED;
+    DeviceGuard g(cg->ctx->device);
+    hipStream_t s = cg->ctx->stream;
+    const size_t bytes = (size_t)cg->n * (size_t)bs * sizeof(double);
+    CGX_HIP(hipMalloc(&own, bytes));
+    int rc;
+    if (kind == CGX_BLOCK_JACOBI) {
+      rc = block_inv_impl(cg->A, bs, own);
+    } else {
+      unsigned long long h[2];
+      hipError_t e = hipMemcpyAsync(own, d_w, bytes, hipMemcpyDeviceToDevice, s);
+      rc = e == hipSuccess ? CGX_OK : hip_fail(e, "cgx_cg_set_block_precond (the copy of d_w)");
+      if (!rc)
+        rc = pc_scan(cg->ctx, h, [&](unsigned long long *bad) {
+          return blk_check(cg->n, bs, (const double *)own, bad, s);
+        });
+      if (!rc && h[0] != 0) {
+        set_error("cgx_cg_set_block_precond: %llu row(s) of d_w with an entry that is not finite "
+                  "or a diagonal entry that is not positive and finite; the first is row %llu "
+                  "(block %llu)", h[0], h[1], h[1] / (unsigned long long)bs);
+        rc = CGX_EINVAL;
+      }
+    }
+    if (rc) {
+      (void)hipStreamSynchronize(s);
+      (void)hipFree(own);
+      return rc;
+    }
+  }
+  DeviceGuard g(cg->ctx->device);
+  // the solve in progress ends here; nothing queued may still read the old W or m
+  CGX_HIP(hipStreamSynchronize(cg->ctx->stream));
+  drop_graph(cg, cg->graphs);
+  drop_graph(cg, cg->bt.graphs);
+  cg->begun = false;
+  cg->bt.begun = false;
+  if (cg->blk_w) (void)hipFree(cg->blk_w);
+  cg->blk_w = own;
+  cg->blk_kind = kind;
+  cg->blk_bs = kind == CGX_BLOCK_NONE ? 0 : bs;
+  // the two families exclude each other: this call replaces a diagonal one
+  if (cg->minv_own) (void)hipFree(cg->minv_own);
+  cg->minv_own = nullptr;
+  cg->minv = nullptr;
+  cg->precond = CGX_PRECOND_NONE;
+  // auto mode depends on the preconditioner (3 with one, the matrix's own without)
+  if (cg->mode_req == 0) return cgx_cg_set_mode(cg, 0);
+  return CGX_OK;
+}
+
+extern "C" int cgx_cg_get_block_precond(cgx_cg *cg, int *kind, int *bs) {
+  CGX_REQUIRE(cg, CGX_EINVAL, "cg is NULL");
+  if (kind) *kind = cg->blk_kind;
+  if (bs) *bs = cg->blk_bs;
   return CGX_OK;
 }
 
@@ -3593,8 +3737,8 @@ extern "C" int cgx_cg_destroy(cgx_cg *cg) {
   for (hipEvent_t e : cg->run_ev)
     if (e) (void)hipEventDestroy(e);
   for (void *p : {cg->r, cg->p, cg->p2, cg->Ap, cg->st, cg->ws, cg->pk[0], cg->pk[1], cg->pk[2],
-                  cg->coop_ws, cg->coop_trace, cg->minv_own, cg->bt.r, cg->bt.p, cg->bt.Ap,
-                  cg->bt.st, cg->bt.ws, cg->bt.seq_b, cg->bt.seq_x})
+                  cg->coop_ws, cg->coop_trace, cg->minv_own, cg->blk_w, cg->bt.r, cg->bt.p,
+                  cg->bt.Ap, cg->bt.st, cg->bt.ws, cg->bt.seq_b, cg->bt.seq_x})
     if (p) (void)hipFree(p);
   if (cg->bt.h_poll) (void)hipHostFree(cg->bt.h_poll);
   cgx_csr *A = cg->A;
@@ -3665,7 +3809,8 @@ extern "C" int cgx_cg_begin(cgx_cg *cg, const void *b, void *x, double tol,
     if (rc) return rc;
     xe = cg->Ap;
   }
-  if (cg->precond && !precond_mode_ok(cg->mode)) return CGX_ESTATE;
+  if (has_precond(cg) && !precond_mode_ok(cg->mode, cg->blk_kind != CGX_BLOCK_NONE))
+    return CGX_ESTATE;
   rc = with_dtype(cg->dtype, [&](auto t) {
     using T = decltype(t);
     const CgView<T> v(cg);
@@ -3679,6 +3824,10 @@ extern "C" int cgx_cg_begin(cgx_cg *cg, const void *b, void *x, double tol,
       if (e == hipSuccess && cg->precond)
         e = (A->dist ? Launch<T>::pc_init_dist : Launch<T>::pc_init)(cg->n, v.r, v.m, v.P[0],
                                                                      v.st, v.ws, s);
+      if constexpr (std::is_same_v<T, double>) {  // block-Jacobi: p = z = M^-1 r, rz[0] = r.z
+        if (e == hipSuccess && cg->blk_kind != CGX_BLOCK_NONE)
+          e = blk_init(cg->n, cg->blk_bs, v.r, (const double *)cg->blk_w, v.P[0], v.st, v.ws, s);
+      }
       return e;
     });
     if (rc || !A->dist) return rc;
@@ -3832,7 +3981,7 @@ extern "C" int cgx_cg_rxr(cgx_cg *cg, double *rxr) {
 
 extern "C" int cgx_cg_rz(cgx_cg *cg, double *rz) {
   CGX_REQUIRE(cg && rz, CGX_EINVAL, "NULL argument");
-  CGX_REQUIRE(cg->precond, CGX_ESTATE, "cgx_cg_rz without a preconditioner");
+  CGX_REQUIRE(has_precond(cg), CGX_ESTATE, "cgx_cg_rz without a preconditioner");
   CGX_REQUIRE(cg->begun, CGX_ESTATE, "cgx_cg_rz before cgx_cg_begin");
   DeviceGuard g(cg->ctx->device);
   hipStream_t s = cg->ctx->stream;
@@ -3874,7 +4023,7 @@ using BSt = CgScalars<double>;
 const char *batch_fused_refusal(const cgx_cg *cg) {
   if (cg->A->dist) return "the matrix is partitioned (cgx_csr_create_dist)";
   if (cg->dtype != CGX_F64) return "the solver is f32 (the fused form is f64)";
-  if (cg->precond) return "a preconditioner is set (the fused form is unpreconditioned)";
+  if (has_precond(cg)) return "a preconditioner is set (the fused form is unpreconditioned)";
   return nullptr;
 }
 // auto: fused for two or more columns where the matrix's production variant

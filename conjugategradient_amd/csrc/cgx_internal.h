@@ -524,6 +524,32 @@ hipError_t cg_coop(int64_t n, int R, bool streamed, const int *rowptr, const int
                    unsigned long long *trace, int stall, hipStream_t s);
 constexpr int kCoopTraceWords = kCoopMaxG * 8 * 8;  // workgroups x bodies 8-15 x phases
 
+// ---- block-Jacobi preconditioning (f64, one device; cgx_kernels.hip)
+// W (n x bs row-major, 1 <= bs <= 8): row i holds row i - b bs of block b's
+// W_b, block b over rows [b bs, min((b + 1) bs, n)).
+// blk_inv: out = the inverses of A's diagonal blocks; bad[0] counts the blocks
+// with a pivot that is not positive and finite, bad[1] is the lowest such
+// block (the caller presets {0, ~0}). blk_check: the rows of a caller's W with
+// a non-finite entry in a real column or a diagonal entry that is not
+// positive and finite, counted the same way.
+hipError_t blk_inv(const CsrDev &A, int bs, double *out, unsigned long long *bad, hipStream_t s);
+hipError_t blk_check(int64_t n, int bs, const double *W, unsigned long long *bad, hipStream_t s);
+// after cg_init: p = z = M^-1 r, rz[0] = r.z
+hipError_t blk_init(int64_t n, int bs, const double *r, const double *W, double *p,
+                    CgScalars<double> *st, RedWs<double> *ws, hipStream_t s);
+// the three-kernel body's vector kernels (modes 1 and 3): update_r stores z
+// over Ap (apz) and leaves blk_update_parts(n, bs) partials of r.r and r.z;
+// the p updates read z there
+int blk_update_parts(int64_t n, int bs);
+hipError_t blk_update_r(int64_t n, int bs, double *r, double *apz, const double *W,
+                        CgScalars<double> *st, int slot, RedWs<double> *ws, hipStream_t s,
+                        int np_pap, int rev);
+hipError_t blk_update_xp(int64_t n, double *x, double *p, const double *z, CgScalars<double> *st,
+                         int slot, RedWs<double> *ws, int np_rr, hipStream_t s, int rev);
+hipError_t blk_update_p_defer(int64_t n, double *x, const double *p, double *pn,
+                              double *const P[4], const double *z, CgScalars<double> *st,
+                              int slot, RedWs<double> *ws, int np_rr, hipStream_t s, int rev);
+
 // value-code templates (cgx_abi.cpp build_value_templates): per slice the
 // hash of its 4-bit code chunk (0: wider than one chunk); the template slice
 // table of nt templates, exact byte matches only (*count: matched slices)

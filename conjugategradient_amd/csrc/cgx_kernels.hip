@@ -6275,6 +6275,481 @@ __global__ __launch_bounds__(kBlock) void k_diag_check(int64_t n, const T *__res
   }
 }
 
+// ---------------------------------------------------------------------------
+// Block-Jacobi preconditioning (cgx_cg_set_block_precond), f64
+// on one device: M^-1 = blockdiag(W_b), block b over rows [b bs, min((b + 1)
+// bs, n)), 1 <= bs <= 8, W stored n x bs row-major (W[i bs + j] = W_b[i - b bs,
+// j]; the columns past a partial last block are +0.0 and never multiplied).
+// z_i = sum_j W[i bs + j] r_{b bs + j}: from +0.0, ascending j, each product
+// rounded before its add. update_r forms z from the updated r of its tile in
+// LDS and stores it over Ap (dead after that kernel in modes 1 and 3); the p
+// updates read z there and touch neither r nor W. Everything else — the
+// partials, the stop rule, the deferred-x records — is the diagonal kernels'.
+// ---------------------------------------------------------------------------
+constexpr int kBlkTile = 512;   // rows per tile before rounding down to whole blocks (bs <= 8)
+constexpr int kGridUpdateRBlk = 512;
+// rows of a tile of k_update_r_blk: whole blocks only
+__host__ __device__ constexpr int blk_tile_rows(int bs) { return (kBlkTile / bs) * bs; }
+
+// W_b = (diagonal block b of A)^-1 by LDL^T without pivoting, statement for
+// statement tests/bj_model.py block_inverse. One thread per block. Row i of
+// the block takes the entries of CSR row i with b0 <= col <= i (the lower
+// triangle decides; duplicates summed from 0 in entry order; rows may be
+// unsorted). A pivot that is not positive and finite makes the block bad:
+// bad[0] counts such blocks, bad[1] keeps the lowest one's index.
+template <int BS>
+__global__ __launch_bounds__(kBlock) void k_block_inv(int64_t n, const int *__restrict__ rowptr,
+                                                      const int *__restrict__ col,
+                                                      const double *__restrict__ val,
+                                                      double *__restrict__ out,
+                                                      unsigned long long *bad) {
+  const int64_t nb = (n + BS - 1) / BS;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x; b < nb; b += stride) {
+    const int64_t b0 = b * BS;
+    const int m = (int)min((int64_t)BS, n - b0);  // rows of this block
+    double B[BS][BS], L[BS][BS], M[BS][BS], D[BS], E[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+#pragma unroll
+      for (int j = 0; j <= i; ++j) B[i][j] = 0.0;
+      if (i < m) {
+        for (int k = rowptr[b0 + i]; k < rowptr[b0 + i + 1]; ++k) {
+          const int64_t c = (int64_t)col[k] - b0;
+          const double v = val[k];
+#pragma unroll
+          for (int j = 0; j <= i; ++j)
+            if (c == j) B[i][j] = B[i][j] + v;
+        }
+      }
+    }
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < BS; ++j) {
+      if (j < m) {
+        double s = B[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) s = s - L[j][k] * (L[j][k] * D[k]);
+        D[j] = s;
+        if (!pc_ok(s)) ok = false;
+#pragma unroll
+        for (int i = j + 1; i < BS; ++i) {
+          if (i < m) {
+            double t = B[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) t = t - L[i][k] * (L[j][k] * D[k]);
+            L[i][j] = t / s;
+          }
+        }
+        E[j] = 1.0 / s;
+      }
+    }
+    // M = L^-1 (unit lower triangle): M[i][j] = -(L[i][j] + sum_{j<k<i} L[i][k] M[k][j])
+#pragma unroll
+    for (int i = 1; i < BS; ++i) {
+      if (i < m) {
+#pragma unroll
+        for (int j = 0; j < i; ++j) {
+          double s = L[i][j];
+#pragma unroll
+          for (int k = j + 1; k < i; ++k) s = s + L[i][k] * M[k][j];
+          M[i][j] = -s;
+        }
+      }
+    }
+    // W = M^T D^-1 M, the lower triangle computed and mirrored
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+      if (i < m) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+          double s = j == i ? E[i] : M[i][j] * E[i];
+#pragma unroll
+          for (int k = i + 1; k < BS; ++k)
+            if (k < m) s = s + (M[k][i] * E[k]) * (j == i ? M[k][i] : M[k][j]);
+          out[(b0 + i) * BS + j] = s;
+          out[(b0 + j) * BS + i] = s;
+        }
+#pragma unroll
+        for (int j = 0; j < BS; ++j)
+          if (j >= m) out[(b0 + i) * BS + j] = 0.0;
+      }
+    }
+    if (!ok) {
+      atomicAdd(&bad[0], 1ull);
+      atomicMin(&bad[1], (unsigned long long)b);
+    }
+  }
+}
+
+// a caller's W: every entry of a real column finite, every W_b[i, i] positive
+// and finite (pc_ok). bad[0] counts the rows that fail, bad[1] the lowest.
+__global__ __launch_bounds__(kBlock) void k_block_check(int64_t n, int bs,
+                                                        const double *__restrict__ W,
+                                                        unsigned long long *bad) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    const int64_t b0 = (i / bs) * bs;
+    const int nc = (int)min((int64_t)bs, n - b0);
+    bool ok = pc_ok(W[i * bs + (i - b0)]);
+    for (int j = 0; j < nc; ++j) {
+      const double w = W[i * bs + j];
+      if (!(fabs(w) <= std::numeric_limits<double>::max())) ok = false;  // NaN, Inf
+    }
+    if (!ok) {
+      atomicAdd(&bad[0], 1ull);
+      atomicMin(&bad[1], (unsigned long long)i);
+    }
+  }
+}
+
+// after k_cg_init: p = z = M^-1 r and rz[0] = r.z (r read from memory: once
+// per solve)
+__global__ __launch_bounds__(kBlock) void k_pc_init_blk(int64_t n, int bs,
+                                                        const double *__restrict__ r,
+                                                        const double *__restrict__ W,
+                                                        double *__restrict__ p,
+                                                        CgScalars<double> *st,
+                                                        RedWs<double> *ws) {
+  __shared__ double red[8];
+  __shared__ int flag;
+  Dd<double> acc(0.0);
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    const int64_t b0 = (i / bs) * bs;
+    const int nc = (int)min((int64_t)bs, n - b0);
+    double z = 0.0;
+    for (int j = 0; j < nc; ++j) z = z + W[i * bs + j] * r[b0 + j];
+    p[i] = z;
+    acc += r[i] * z;
+  }
+  if (grid_reduce_dd(acc, ws, red, &flag) && threadIdx.x == 0) st->rz[0] = acc.value();
+}
+
+// r = r - alpha Ap with alpha = rz / p.Ap, z = M^-1 r stored over Ap, r.r and
+// r.z in one sweep (k_update_r_pc's place in the body). A workgroup walks
+// tiles of blk_tile_rows(BS) rows (whole blocks), tile E(j) for j = blockIdx,
+// + gridDim, ..; thread t owns the tile's rows t and t + 256. The tile's
+// updated r goes through LDS behind one barrier (the active test is uniform),
+// then each thread forms z for its rows from its row of W and the block's r.
+// Ap[i] is read and z[i] written by the same thread.
+template <int BS, bool SNT, int KP>
+__device__ __forceinline__ void update_r_blk_body(int64_t n, double *r, double *apz,
+                                                  const double *__restrict__ W,
+                                                  CgScalars<double> *st, int slot,
+                                                  RedWs<double> *ws, int np_pap, int rev) {
+  constexpr int TR = blk_tile_rows(BS);
+  const auto *cst = (const __attribute__((address_space(4))) CgScalars<double> *)st;
+  const bool act = cst->active[slot] != 0;  // branched on after the first loads
+  __shared__ double red[8];
+  __shared__ double redz[8];
+  __shared__ double rs[TR];
+  const int64_t ntile = (n + TR - 1) / TR;
+  auto E = [&](int64_t j) { return rev ? ntile - 1 - j : j; };  // sweep direction
+  const double rz = cst->rz[slot];
+  Dd<double> pl[KP];
+  parts_load(ws->pap_part, np_pap, pl);
+  double rv[2], av[2], wv[2][BS];
+  // a tile's loads, clamped to the tile and to n: no branch
+  auto loads = [&](int64_t t0) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int64_t i = min(t0 + min((int)threadIdx.x + u * kBlock, TR - 1), n - 1);
+      rv[u] = r[i];
+      av[u] = ldg<SNT>(apz + i);  // Ap is dead once z is stored over it
+#pragma unroll
+      for (int j = 0; j < BS; ++j) wv[u][j] = W[i * BS + j];
+    }
+  };
+  int64_t j = blockIdx.x;  // (the grid has at most ntile workgroups)
+  loads(E(j) * TR);
+  if (!act) {
+    keep(rz);
+    keep(pl);
+    keep(rv);
+    keep(av);
+    keep(wv[0]);
+    keep(wv[1]);
+    return;
+  }
+  const double pAp = parts_sum_dd(pl, np_pap, red).value();
+  const double alpha = rz / pAp;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {  // the record; the deferred x update
+    st->pAp[slot] = pAp;
+    st->alpha[slot] = alpha;
+    st->skip[slot] = 0;
+  }
+  Dd<double> acc(0.0), accz(0.0);  // r.r and r.z (double-length)
+  for (bool first = true; j < ntile; j += gridDim.x, first = false) {
+    const int64_t t0 = E(j) * TR;
+    if (!first) {
+      __syncthreads();  // the previous tile's r in LDS has been read
+      loads(t0);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int l = (int)threadIdx.x + u * kBlock;
+      if (l < TR && t0 + l < n) {
+        rv[u] = rv[u] - alpha * av[u];
+        r[t0 + l] = rv[u];
+        rs[l] = rv[u];
+        acc += rv[u] * rv[u];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int l = (int)threadIdx.x + u * kBlock;
+      if (l < TR && t0 + l < n) {
+        const int b0 = (l / BS) * BS;
+        const int64_t nc = n - (t0 + b0);  // the block's real columns (>= BS but in the last)
+        double z = 0.0;
+#pragma unroll
+        for (int q = 0; q < BS; ++q)
+          if (q < nc) z = z + wv[u][q] * rs[b0 + q];
+        apz[t0 + l] = z;
+        accz += rv[u] * z;
+      }
+    }
+  }
+  // this workgroup's shares of the two dots; the next kernel sums them
+  acc = block_sum_dd(acc, red);
+  accz = block_sum_dd(accz, redz);
+  if (threadIdx.x == 0) {
+    ws->rr_part[2 * blockIdx.x] = acc.hi;
+    ws->rr_part[2 * blockIdx.x + 1] = acc.lo;
+    ws->rz_part[2 * blockIdx.x] = accz.hi;
+    ws->rz_part[2 * blockIdx.x + 1] = accz.lo;
+  }
+}
+template <int BS, int KP>
+__global__ __launch_bounds__(kBlock) void k_update_r_blk(int64_t n, double *r, double *apz,
+                                                         const double *__restrict__ W,
+                                                         CgScalars<double> *st, int slot,
+                                                         RedWs<double> *ws, int np_pap,
+                                                         int rev) {
+  if (stream_nt<double>(n))
+    update_r_blk_body<BS, true, KP>(n, r, apz, W, st, slot, ws, np_pap, rev);
+  else
+    update_r_blk_body<BS, false, KP>(n, r, apz, W, st, slot, ws, np_pap, rev);
+}
+
+// mode 1: x = x + alpha p ; p = z + beta p ; stop rule (k_update_xp_pc with z
+// read from the Ap buffer where that kernel forms m o r)
+__global__ __launch_bounds__(kBlock) void k_update_xp_blk(int64_t n, double *__restrict__ x,
+                                                          double *__restrict__ p,
+                                                          const double *__restrict__ z,
+                                                          CgScalars<double> *st, int slot,
+                                                          RedWs<double> *ws, int np_rr,
+                                                          int rev) {
+  const int nxt = (slot + 1) & 3;
+  if (!st->active[slot]) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->active[nxt] = 0;
+    return;
+  }
+  __shared__ double red[8];
+  __shared__ double redz[8];
+  const double rxr = st->rxr[slot];
+  const double rz = st->rz[slot];
+  const double alpha = rz / st->pAp[slot];
+  const double rr = sum_parts_dd(ws->rr_part, np_rr, red).value();
+  const double rzn = sum_parts_dd(ws->rz_part, np_rr, redz).value();
+  const double beta = rzn / rz;
+  const int64_t n2 = n >> 1;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  double2 *x2 = reinterpret_cast<double2 *>(x);
+  double2 *p2 = reinterpret_cast<double2 *>(p);
+  const double2 *z2 = reinterpret_cast<const double2 *>(z);
+  auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  for (; i + 3 * stride < n2; i += 4 * stride) {
+    double2 xv[4], pv[4], zv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      xv[u] = x2[E(i + u * stride)];
+      pv[u] = p2[E(i + u * stride)];
+      zv[u] = z2[E(i + u * stride)];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      xv[u].x = xv[u].x + alpha * pv[u].x;
+      xv[u].y = xv[u].y + alpha * pv[u].y;
+      pv[u].x = zv[u].x + beta * pv[u].x;
+      pv[u].y = zv[u].y + beta * pv[u].y;
+      x2[E(i + u * stride)] = xv[u];
+      p2[E(i + u * stride)] = pv[u];
+    }
+  }
+  for (; i < n2; i += stride) {
+    double2 xv = x2[E(i)], pv = p2[E(i)];
+    const double2 zv = z2[E(i)];
+    xv.x = xv.x + alpha * pv.x;
+    xv.y = xv.y + alpha * pv.y;
+    pv.x = zv.x + beta * pv.x;
+    pv.y = zv.y + beta * pv.y;
+    x2[E(i)] = xv;
+    p2[E(i)] = pv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (n & 1) {
+      const double pv = p[n - 1];
+      x[n - 1] = x[n - 1] + alpha * pv;
+      p[n - 1] = z[n - 1] + beta * pv;
+    }
+    pc_stop_rule(st, slot, rxr, rr, rzn);
+  }
+}
+
+// mode 3: p_{k+1} = z + beta p_k into the next p buffer, the stop rule, and in
+// slot 3 (FLUSH) the group's x updates (update_p_defer_pc_body's single-device
+// form with z read from the Ap buffer)
+template <bool FLUSH, bool SNT>
+__device__ __forceinline__ void update_p_defer_blk_body(int64_t n, double *__restrict__ x,
+                                                        const double *p, double *pn,
+                                                        const double *P0, const double *P1,
+                                                        const double *P2,
+                                                        const double *__restrict__ z,
+                                                        CgScalars<double> *st, int slot,
+                                                        RedWs<double> *ws, int np_rr, int rev) {
+  using T = double;
+  using V = double2;
+  const int nxt = (slot + 1) & 3;
+  // the flag, rxr, rz and both dots' partials in one round trip
+  const auto *cst = (const __attribute__((address_space(4))) CgScalars<T> *)st;
+  const bool act = cst->active[slot] != 0;
+  const T rxr = cst->rxr[slot];
+  const T rz = cst->rz[slot];
+  Dd<T> pl[kPartsPerThread], plz[kPartsPerThread];
+  parts_load_np(ws->rr_part, np_rr, pl);
+  parts_load_np(ws->rz_part, np_rr, plz);
+  const int64_t n2 = n >> 1;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const V *p2 = reinterpret_cast<const V *>(p);
+  const V *z2 = reinterpret_cast<const V *>(z);
+  // the non-flushing body: this thread's first four elements of p_k and z go
+  // out with the partials, before beta (clamped; for n = 1 one element past
+  // the end: both from the Ap buffer, which carries a slack element)
+  V pv0[4], zv0[4];
+  if constexpr (!FLUSH) {
+    const V *p2f = n2 > 0 ? p2 : z2;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t j = n2 > 0 ? E(min(i + u * stride, n2 - 1)) : 0;
+      pv0[u] = ldv<SNT, T>(p2f + j);
+      zv0[u] = ldv<SNT, T>(z2 + j);
+    }
+  }
+  if (!act) {
+    keep(rxr);
+    keep(rz);
+    keep(pl);
+    keep(plz);
+    if constexpr (!FLUSH) {
+      keep(pv0);
+      keep(zv0);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->active[nxt] = 0;
+    return;
+  }
+  __shared__ T red[8];
+  __shared__ T redz[8];
+  const T rr = parts_sum_dd(pl, np_rr, red).value();
+  const T rzn = parts_sum_dd(plz, np_rr, redz).value();
+  const T beta = rzn / rz;
+  // slot-3 flush: alphas and skips of the group, written by earlier launches
+  T a[4] = {T(0), T(0), T(0), T(0)};
+  bool use[4] = {false, false, false, false};
+  if constexpr (FLUSH) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      a[t] = st->alpha[t];
+      use[t] = st->skip[t] == 0;
+    }
+  }
+  V *pn2 = reinterpret_cast<V *>(pn);
+  V *x2 = reinterpret_cast<V *>(x);
+  const V *Q[3] = {reinterpret_cast<const V *>(P0), reinterpret_cast<const V *>(P1),
+                   reinterpret_cast<const V *>(P2)};
+  auto body = [&](int64_t i) {
+    const V pv = ldv<SNT, T>(p2 + i);
+    const V zv = ldv<SNT, T>(z2 + i);
+    V q[3], xv;
+    if constexpr (FLUSH) {  // x and the old p buffers: not read again soon
+      xv = ldv<SNT, T>(x2 + i);
+#pragma unroll
+      for (int t = 0; t < 3; ++t) q[t] = ldv<SNT, T>(Q[t] + i);  // before pn (= P0) is written
+    }
+    V o;
+    o.x = zv.x + beta * pv.x;
+    o.y = zv.y + beta * pv.y;
+    if constexpr (FLUSH) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        if (use[t]) {
+          xv.x = xv.x + a[t] * q[t].x;
+          xv.y = xv.y + a[t] * q[t].y;
+        }
+      }
+      if (use[3]) {
+        xv.x = xv.x + a[3] * pv.x;
+        xv.y = xv.y + a[3] * pv.y;
+      }
+      stv<SNT, T>(x2 + i, xv);
+    }
+    pn2[i] = o;
+  };
+  if constexpr (!FLUSH) {
+    // the first block from the early loads (a block past the end: its
+    // clamped loads are not stored)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (i + u * stride < n2) {
+        V o;
+        o.x = zv0[u].x + beta * pv0[u].x;
+        o.y = zv0[u].y + beta * pv0[u].y;
+        pn2[E(i + u * stride)] = o;
+      }
+    }
+    i += 4 * stride;
+  }
+  for (; i + 3 * stride < n2; i += 4 * stride) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) body(E(i + u * stride));
+  }
+  for (; i < n2; i += stride) body(E(i));
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (n & 1) {
+      const T pv = p[n - 1];
+      if constexpr (FLUSH) {
+        T xv = x[n - 1];
+        const T *Ps[4] = {P0, P1, P2, p};
+        for (int t = 0; t < 4; ++t)
+          if (use[t]) xv = xv + a[t] * Ps[t][n - 1];
+        x[n - 1] = xv;
+      }
+      pn[n - 1] = z[n - 1] + beta * pv;
+    }
+    pc_stop_rule(st, slot, rxr, rr, rzn);
+    if constexpr (FLUSH) {
+      for (int t = 0; t < 4; ++t) st->ran[t] = 0;
+    } else {
+      st->ran[slot] = 1;
+    }
+  }
+}
+template <bool FLUSH>
+__global__ __launch_bounds__(kBlock) void k_update_p_defer_blk(
+    int64_t n, double *__restrict__ x, const double *p, double *pn, const double *P0,
+    const double *P1, const double *P2, const double *__restrict__ z, CgScalars<double> *st,
+    int slot, RedWs<double> *ws, int np_rr, int rev) {
+  if (stream_nt<double>(n))
+    update_p_defer_blk_body<FLUSH, true>(n, x, p, pn, P0, P1, P2, z, st, slot, ws, np_rr, rev);
+  else
+    update_p_defer_blk_body<FLUSH, false>(n, x, p, pn, P0, P1, P2, z, st, slot, ws, np_rr, rev);
+}
+
 // *dst = sum of part[0..np) in sum_parts order (partitioned runs: the local
 // dot before its RCCL all-reduce)
 template <typename T>
@@ -7254,6 +7729,82 @@ template <typename T>
 hipError_t Launch<T>::diag_check(int64_t n, const T *m, unsigned long long *bad, hipStream_t s) {
   CGX_LAUNCH(k_diag_check<T>, elem_grid(n, 4), n, m, bad);
 }
+// ---- block-Jacobi preconditioning (f64, one device)
+hipError_t blk_inv(const CsrDev &A, int bs, double *out, unsigned long long *bad,
+                   hipStream_t s) {
+  const int64_t nb = (A.n + bs - 1) / bs;
+#define CGX_BINV(BS)                                                                      \
+  case BS:                                                                                \
+    CGX_LAUNCH(k_block_inv<BS>, elem_grid(nb, 1), A.n, A.rowptr, A.col,                   \
+               (const double *)A.val, out, bad)
+  switch (bs) {
+    CGX_BINV(1);
+    CGX_BINV(2);
+    CGX_BINV(3);
+    CGX_BINV(4);
+    CGX_BINV(5);
+    CGX_BINV(6);
+    CGX_BINV(7);
+    CGX_BINV(8);
+  }
+#undef CGX_BINV
+  return hipErrorInvalidValue;
+}
+hipError_t blk_check(int64_t n, int bs, const double *W, unsigned long long *bad,
+                     hipStream_t s) {
+  CGX_LAUNCH(k_block_check, elem_grid(n, 4), n, bs, W, bad);
+}
+hipError_t blk_init(int64_t n, int bs, const double *r, const double *W, double *p,
+                    CgScalars<double> *st, RedWs<double> *ws, hipStream_t s) {
+  CGX_LAUNCH(k_pc_init_blk, Launch<double>::grid_elems(n, kGridUpdateP), n, bs, r, W, p, st, ws);
+}
+int blk_update_parts(int64_t n, int bs) {
+  const int tr = blk_tile_rows(bs);
+  const int64_t nt = (n + tr - 1) / tr;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(nt, kGridUpdateRBlk));
+}
+hipError_t blk_update_r(int64_t n, int bs, double *r, double *apz, const double *W,
+                        CgScalars<double> *st, int slot, RedWs<double> *ws, hipStream_t s,
+                        int np_pap, int rev) {
+  if (np_pap < 1 || n < 1) return hipErrorInvalidValue;
+  const int g = blk_update_parts(n, bs);
+#define CGX_URB(BS)                                                                       \
+  case BS:                                                                                \
+    if (np_pap <= 4 * kBlock)                                                             \
+      CGX_LAUNCH((k_update_r_blk<BS, 4>), g, n, r, apz, W, st, slot, ws, np_pap, rev);    \
+    CGX_LAUNCH((k_update_r_blk<BS, kPartsPerThread>), g, n, r, apz, W, st, slot, ws,      \
+               np_pap, rev)
+  switch (bs) {
+    CGX_URB(1);
+    CGX_URB(2);
+    CGX_URB(3);
+    CGX_URB(4);
+    CGX_URB(5);
+    CGX_URB(6);
+    CGX_URB(7);
+    CGX_URB(8);
+  }
+#undef CGX_URB
+  return hipErrorInvalidValue;
+}
+hipError_t blk_update_xp(int64_t n, double *x, double *p, const double *z, CgScalars<double> *st,
+                         int slot, RedWs<double> *ws, int np_rr, hipStream_t s, int rev) {
+  if (np_rr < 1) return hipErrorInvalidValue;
+  CGX_LAUNCH(k_update_xp_blk, Launch<double>::grid_elems(n, kGridUpdateP), n, x, p, z, st, slot,
+             ws, np_rr, rev);
+}
+hipError_t blk_update_p_defer(int64_t n, double *x, const double *p, double *pn,
+                              double *const P[4], const double *z, CgScalars<double> *st,
+                              int slot, RedWs<double> *ws, int np_rr, hipStream_t s, int rev) {
+  if (np_rr < 1) return hipErrorInvalidValue;
+  const int g = Launch<double>::grid_elems(n, kGridUpdateP);
+  if (slot == 3)
+    CGX_LAUNCH(k_update_p_defer_blk<true>, g, n, x, p, pn, (const double *)P[0],
+               (const double *)P[1], (const double *)P[2], z, st, slot, ws, np_rr, rev);
+  CGX_LAUNCH(k_update_p_defer_blk<false>, g, n, x, p, pn, (const double *)P[0],
+             (const double *)P[1], (const double *)P[2], z, st, slot, ws, np_rr, rev);
+}
+
 template <typename T>
 hipError_t Launch<T>::dot_acc(int64_t n, const T *x, const T *y, T *res, RedWs<T> *ws,
                               hipStream_t s) {

@@ -266,6 +266,12 @@ struct cgx_cg {
   const void *minv = nullptr;
   void *minv_own = nullptr;
   bool minv_nt = false;  // $CGX_PCG_M_NT=1: m through non-temporal loads (A/B)
+  // block-Jacobi preconditioning (cgx_cg_set_block_precond; excludes the
+  // diagonal one: precond is NONE while blk_kind is set): the kind, the block
+  // size and the solver's own W (n x blk_bs doubles, row-major)
+  int blk_kind = CGX_BLOCK_NONE;
+  int blk_bs = 0;
+  void *blk_w = nullptr;
   void *st = nullptr;   // cgx::CgScalars<T>
   void *ws = nullptr;   // cgx::RedWs<T>
   const void *b = nullptr;

@@ -77,6 +77,51 @@ def irregular_spd(n: int, mean_deg: float = 3.8, seed: int = 12345, hub: int = 0
     return coo_to_csr(n, rows, cols, vals)
 
 
+def node_mixed_blocks(n_nodes: int, bs: int, e: float, seed: int = 7):
+    """The node matrices T_k = Q diag(10^U(0, e)) Q'^T of node_mixed, (n_nodes,
+    bs, bs): Q, Q' orthogonal (QR of Gaussian matrices), from one seeded
+    generator."""
+    rng = np.random.default_rng(seed)
+    q, _ = np.linalg.qr(rng.standard_normal((n_nodes, bs, bs)))
+    q2, _ = np.linalg.qr(rng.standard_normal((n_nodes, bs, bs)))
+    sv = 10.0 ** rng.uniform(0.0, e, (n_nodes, bs))
+    return np.einsum("kij,kj,kmj->kim", q, sv, q2)
+
+
+def node_mixed(nx: int, ny: int, bs: int, e: float, seed: int = 7):
+    """A = D^T (L (x) I_bs) D as CSR (rowptr, col, val): L the 5-point
+    Laplacian on nx x ny nodes (node k = y nx + x), bs unknowns per node, D =
+    blockdiag(T_k) (node_mixed_blocks): a vector-valued problem whose
+    conditioning sits inside each node's dense bs x bs block, where a diagonal
+    preconditioner does nothing and block-Jacobi undoes it. Built block-sparse,
+    with no dense matrix: block (k, l) = L_kl T_k^T T_l for l >= k (the
+    diagonal block's upper triangle), mirrored as its transpose, so A is
+    exactly symmetric. n = nx ny bs rows, at most 5 bs entries per row."""
+    nn = nx * ny
+    T = node_mixed_blocks(nn, bs, e, seed)
+    k = np.arange(nn)
+    x, y = k % nx, k // nx
+    ii, mm = np.meshgrid(np.arange(bs), np.arange(bs), indexing="ij")
+    rows, cols, vals = [], [], []
+    # diagonal blocks: 4 T_k^T T_k, the upper triangle mirrored
+    G = 4.0 * np.einsum("kji,kjm->kim", T, T)
+    up = np.triu(np.ones((bs, bs), bool))
+    G = np.where(up, G, np.swapaxes(G, 1, 2))
+    rows.append((k[:, None, None] * bs + ii).ravel())
+    cols.append((k[:, None, None] * bs + mm).ravel())
+    vals.append(G.ravel())
+    for sel, step in ((x < nx - 1, 1), (y < ny - 1, nx)):
+        a = k[sel]
+        b = a + step
+        blk = -np.einsum("kji,kjm->kim", T[a], T[b])  # L_kl = -1
+        r = (a[:, None, None] * bs + ii).ravel()
+        c = (b[:, None, None] * bs + mm).ravel()
+        rows += [r, c]
+        cols += [c, r]
+        vals += [blk.ravel(), blk.ravel()]
+    return coo_to_csr(nn * bs, np.concatenate(rows), np.concatenate(cols), np.concatenate(vals))
+
+
 @dataclass
 class Slab:
     """One rank's rows of a workload, in HBM (int32 rowptr/col, f64 val)."""

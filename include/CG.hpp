@@ -60,6 +60,15 @@ enum class Preconditioner { None = CGX_PRECOND_NONE, Jacobi = CGX_PRECOND_JACOBI
                             Diagonal = CGX_PRECOND_DIAGONAL };
 
 /**
+ * Extension (not in the reference): block-Jacobi preconditioning of solve(),
+ * cgx.h's CGX_BLOCK_* kinds, with dense diagonal blocks of 1 to 8 rows.
+ * Jacobi: the inverses of A's diagonal blocks, built on the device; Given:
+ * N x block_size row-major values the caller supplies.
+ */
+enum class BlockPreconditioner { None = CGX_BLOCK_NONE, Jacobi = CGX_BLOCK_JACOBI,
+                                 Given = CGX_BLOCK_GIVEN };
+
+/**
  * @class CG (CG.hpp:53-601)
  * Set matrix, right-hand side and optional initial guess, solve, extract.
  */
@@ -217,15 +226,56 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
                                   "setPreconditioner(Vector &&)");
     _precond = kind;
     _minv = Vector(_queue);
+    drop_block();
     if (_solver) apply_precond(_solver.get());
   }
   /** Diagonal: minv (N positive, finite values on the device) is moved in */
   void setPreconditioner(Vector &&minv) {
     _minv = std::forward<Vector>(minv);
     _precond = Preconditioner::Diagonal;
+    drop_block();
     if (_solver) apply_precond(_solver.get());
   }
   Preconditioner preconditioner() const { return _precond; }
+  /**
+   * Block-Jacobi preconditioning of the following solves (cgx.h
+   * cgx_cg_set_block_precond: f64, modes 1 and 3): None, or Jacobi with
+   * block_size rows per block (1..8). It replaces a preconditioner set by
+   * setPreconditioner and is replaced by it. Given needs its values: the
+   * overload below.
+   * @throw std::invalid_argument for Given, or a block size outside 1..8
+   */
+  void setBlockPreconditioner(BlockPreconditioner kind, int block_size = 0) {
+    if (kind == BlockPreconditioner::Given)
+      throw std::invalid_argument("BlockPreconditioner::Given needs its values: "
+                                  "setBlockPreconditioner(int, Vector &&)");
+    if (kind != BlockPreconditioner::None && (block_size < 1 || block_size > 8))
+      throw std::invalid_argument("setBlockPreconditioner: block_size must be 1..8");
+    _blk = kind;
+    _blk_bs = kind == BlockPreconditioner::None ? 0 : block_size;
+    _blk_w = Vector(_queue);
+    _precond = Preconditioner::None;
+    _minv = Vector(_queue);
+    if (_solver) apply_precond(_solver.get());
+  }
+  /**
+   * Given: blocks (N * block_size values on the device, row i's block_size
+   * values its row of its block's matrix) is moved in. Each block must be
+   * symmetric positive definite: the caller's duty, only finite entries and a
+   * positive diagonal are checked.
+   */
+  void setBlockPreconditioner(int block_size, Vector &&blocks) {
+    if (block_size < 1 || block_size > 8)
+      throw std::invalid_argument("setBlockPreconditioner: block_size must be 1..8");
+    _blk_w = std::forward<Vector>(blocks);
+    _blk = BlockPreconditioner::Given;
+    _blk_bs = block_size;
+    _precond = Preconditioner::None;
+    _minv = Vector(_queue);
+    if (_solver) apply_precond(_solver.get());
+  }
+  BlockPreconditioner blockPreconditioner() const { return _blk; }
+  int blockSize() const { return _blk_bs; }
   /**
    * Batched solve (cgx_cg_solve_batch of cgx.h): B.size() = k independent
    * right-hand sides, 1 <= k <= 8, on the matrix in place. X[c] holds column
@@ -319,6 +369,13 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
       _mixed_set = false;
     }
     cgx_mixed *m = _mixed.get();
+    if (_blk != BlockPreconditioner::None) {
+      // refused, whatever the kind: the inner solver is f32 (CGX_EUNSUPPORTED)
+      cgx_cg *inner = nullptr;
+      check(cgx_mixed_inner(m, nullptr, &inner), "solveMixed");
+      check(cgx_cg_set_block_precond(inner, CGX_BLOCK_JACOBI, _blk_bs, nullptr),
+            "setBlockPreconditioner");
+    }
     if (!_mixed_set || _mixed_mode_set != _mixed_mode || _mixed_precond_set != _precond ||
         _mixed_minv_set != _minv.ptr()) {
       // mode before the preconditioner, and None first: whichever of the two
@@ -394,12 +451,30 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
       _solver = std::shared_ptr<cgx_cg>(c, detail::CgDeleter());
       _solver_for = sched;
       // the choice survives a setMatrix (Jacobi is rebuilt from the new matrix)
-      if (_precond != Preconditioner::None) apply_precond(c);
+      if (_precond != Preconditioner::None || _blk != BlockPreconditioner::None)
+        apply_precond(c);
     }
     return _solver.get();
   }
 
+  void drop_block() {  // a diagonal preconditioner replaces a block one
+    _blk = BlockPreconditioner::None;
+    _blk_bs = 0;
+    _blk_w = Vector(_queue);
+  }
+
   void apply_precond(cgx_cg *c) {
+    if (_blk != BlockPreconditioner::None) {
+      const bool given = _blk == BlockPreconditioner::Given;
+      if (given && static_cast<std::size_t>(_blk_w.N()) !=
+                       static_cast<std::size_t>(A.N()) * static_cast<std::size_t>(_blk_bs))
+        throw std::invalid_argument("setBlockPreconditioner: the blocks' length is not "
+                                    "N * block_size");
+      check(cgx_cg_set_block_precond(c, static_cast<int>(_blk), _blk_bs,
+                                     given ? _blk_w.ptr() : nullptr),
+            "setBlockPreconditioner");
+      return;
+    }
     if (_precond == Preconditioner::Diagonal &&
         static_cast<std::size_t>(_minv.N()) != static_cast<std::size_t>(A.N()))
       throw std::invalid_argument("setPreconditioner: the diagonal's length is not N");
@@ -420,6 +495,9 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
   long long _max_iterations = -1;
   Preconditioner _precond = Preconditioner::None;
   Vector _minv{_queue};
+  BlockPreconditioner _blk = BlockPreconditioner::None;
+  int _blk_bs = 0;
+  Vector _blk_w{_queue};
   int _batch_form = 0;
   std::vector<long long> _batch_iterations;
   std::vector<double> _batch_rxr;

@@ -287,7 +287,8 @@ int cgx_cg_config(cgx_cg *cg, int poll_every, int use_graph);
  * whole-matrix lean walks between mode 4's two bounds.
  * The dots are double-length sums (round 6), so modes 1, 3, 4, 6 and 7 give
  * bit-identical x whatever their grids.
- * With a preconditioner set (cgx_cg_set_precond) only modes 1 and 3 run:
+ * With a preconditioner set (cgx_cg_set_precond, cgx_cg_set_block_precond)
+ * only modes 1 and 3 run:
  * auto resolves to 3 whatever the matrix, and modes 2, 4, 5, 6 and 7 return
  * CGX_EUNSUPPORTED. */
 int cgx_cg_set_mode(cgx_cg *cg, int mode);
@@ -363,6 +364,57 @@ int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv);
 int cgx_cg_get_precond(cgx_cg *cg, int *kind);
 /* r.z after the last body (blocking); CGX_ESTATE without a preconditioner */
 int cgx_cg_rz(cgx_cg *cg, double *rz);
+
+/* ---- block-Jacobi preconditioning (replaces nothing in the reference;
+ * DESIGN.md §5f) --------------------------------------------------------------
+ * PCG with M^-1 = blockdiag(W_0, W_1, ...): block b covers rows [b bs,
+ * min((b + 1) bs, n)) with one block size 1 <= bs <= 8 (the last block is
+ * partial when n % bs != 0). W is an n x bs row-major device array, W[i bs + j]
+ * = W_b[i - b bs, j]; the columns past a partial block's size hold +0.0 and
+ * are never multiplied. z_i = sum_j W[i bs + j] r_{b bs + j}, from +0.0 in
+ * ascending j over the block's real columns, each product rounded before its
+ * add. The loop is the diagonal one's with z = M^-1 r in place of m o r; the
+ * stop rule tests the true r.r, and cgx_cg_rxr, the body count and cgx_cg_rz
+ * keep their meanings. update_r stores z over the Ap vector (no new vector);
+ * the p update reads it there: per body (86 + 8 bs) N bytes of vector traffic
+ * against the diagonal form's 94 N.
+ * f64, one device, modes 1 and 3 (auto resolves to 3); modes 2, 4, 5, 6 and 7
+ * return CGX_EUNSUPPORTED from whichever of cgx_cg_set_mode and
+ * cgx_cg_set_block_precond comes second. CGX_EUNSUPPORTED too for an f32
+ * solver (cgx_mixed's inner solver is one), a partitioned matrix and the fused
+ * batch form (the sequential form runs it). The diagonal and the block
+ * preconditioner exclude each other: setting one replaces the other, and
+ * cgx_cg_get_precond reports CGX_PRECOND_NONE while a block one is set.
+ * Out of scope: block sizes that vary, bs > 8, f32, partitioned matrices, the
+ * many-systems solver, the fused batch form, modes 4, 6 and 7. */
+enum { CGX_BLOCK_NONE = 0, CGX_BLOCK_JACOBI = 1, CGX_BLOCK_GIVEN = 2 };
+/* d_out (n * bs values) = W for W_b the inverse of A's diagonal block b.
+ * Row i of a block takes the entries of CSR row i whose column lies in the
+ * block and is <= i: the lower triangle decides, the upper is ignored;
+ * duplicates are summed from 0 in entry order; rows may be unsorted. LDL^T
+ * without pivoting, W = L^-T D^-1 L^-1 with the lower triangle computed and
+ * mirrored (W is exactly symmetric; bs = 1 gives cgx_csr_diag_inv's values).
+ * Blocking. CGX_EINVAL for bs outside 1..8 and when a block has a pivot that
+ * is not positive and finite, a missing diagonal entry included (the message
+ * gives the count of such blocks and the first one's index and first row);
+ * CGX_EUNSUPPORTED for an f32 or a partitioned matrix.
+ * Replaces nothing in the reference. */
+int cgx_csr_block_inv(cgx_csr *A, int bs, void *d_out);
+/* kind NONE: bs and d_w ignored. JACOBI: the solver builds and owns
+ * cgx_csr_block_inv(A, bs) (d_w ignored). GIVEN: d_w = n * bs caller-owned
+ * device values, 16-byte aligned; the solver makes and owns a copy. Checked on
+ * the device (blocking): every entry of a real column finite, every W_b[i, i]
+ * positive and finite (CGX_EINVAL names the first row). That each W_b is
+ * SYMMETRIC and POSITIVE DEFINITE is the caller's duty: CG with another M is
+ * not CG, and nothing here tests it. CGX_EINVAL before any device call for a
+ * NULL handle, an unknown kind, bs outside 1..8, GIVEN with a NULL or
+ * misaligned d_w. Allowed between solves as cgx_cg_set_precond is: it ends the
+ * current solve, drops the captured graphs, and on any error the solver keeps
+ * what it had. Replaces nothing in the reference. */
+int cgx_cg_set_block_precond(cgx_cg *cg, int kind, int bs, const void *d_w);
+/* the block preconditioner in effect (*bs = 0 with CGX_BLOCK_NONE); either
+ * output may be NULL. Replaces nothing in the reference. */
+int cgx_cg_get_block_precond(cgx_cg *cg, int *kind, int *bs);
 
 /* ---- batched CG: several right-hand sides on one matrix (replaces nothing in
  * the reference, whose solve takes one b) ----------------------
@@ -528,7 +580,8 @@ int cgx_mixed_bytes(cgx_mixed *m, int64_t *bytes);
  * assembly; irregular_spd(1000) 6.36 against 2,974 and 37.9.
  * Diagonal preconditioning (cgx_many_set_precond) runs in the same kernel: see
  * there.
- * Out of scope: f32 systems, a preconditioner other than a diagonal, systems
+ * Out of scope: f32 systems, a preconditioner other than a diagonal (the block
+ * one above, cgx_cg_set_block_precond, is the single-system solver's), systems
  * with differing patterns, partitioned or multi-GPU use, and any auto route
  * from cgx_cg_solve into this path; in the wave form (cgx_many_set_form) also
  * several systems per wave for n <= 32 and values cached in registers. */
