@@ -144,6 +144,10 @@ _SIGS = {
     "cgx_many_set_precond": (_i32, [_vp, _i32, _vp, _i64]),
     "cgx_many_get_precond": (_i32, [_vp, C.POINTER(_i32)]),
     "cgx_many_rz": (_i32, [_vp, C.POINTER(_dbl)]),
+    "cgx_many_set_block_precond": (_i32, [_vp, _i32, _i32, _vp, _i64]),
+    "cgx_many_get_block_precond": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "cgx_many_block_inv": (_i32, [_vp, _i32, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "cgx_many_block_bad": (_i32, [_vp, C.POINTER(_i32)]),
     "cgx_many_set_form": (_i32, [_vp, _i32]),
     "cgx_many_get_form": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "cgx_accuracy": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_dbl)]),

@@ -774,7 +774,9 @@ class ManyCG:
     does not fit, n outside 1..4096 or a malformed ``rows``. ``set_values``
     overwrites the values in place for the next solve (no new create).
     ``set_preconditioner`` turns on Jacobi or a caller's diagonal inside the
-    kernel (cgx_many_set_precond); ``rz`` then holds each system's final r.z.
+    kernel (cgx_many_set_precond), ``set_block_preconditioner`` block-Jacobi
+    with dense diagonal blocks of 1 to 8 rows (cgx_many_set_block_precond);
+    the two replace each other, and ``rz`` then holds each system's final r.z.
     ``set_form`` chooses between a workgroup and, for n <= 256, a wave per
     system (cgx_many_set_form); ``form`` is (requested, in effect)."""
 
@@ -808,6 +810,7 @@ class ManyCG:
         self.bodies = self.rxr = self.stopped = self.rz = None
         self._h = None
         self._precond, self._diag = Preconditioner.None_, None
+        self._block, self._blocks = BlockPreconditioner.None_, None
         self._rows = DeviceArray(queue, n + 1, np.int32).upload(rows)
         self._cols = DeviceArray(queue, nnz, np.int32).upload(cols)
         self._vals = DeviceArray(queue, nsys * nnz, np.float64).upload(
@@ -876,7 +879,65 @@ class ManyCG:
         check(lib().cgx_many_set_precond(self._h, int(kind), d_diag.ptr if d_diag else None,
                                          self.n))
         self._precond, self._diag = kind, d_diag  # (the old diag lives until the call above)
+        self._block, self._blocks = BlockPreconditioner.None_, None  # replaced
         self.rz = None
+
+    def set_block_preconditioner(self, kind, block_size: int = 0, blocks=None) -> None:
+        """The next solves' block preconditioner (cgx_many_set_block_precond):
+        ``BlockPreconditioner.None_``, ``Jacobi`` (the inverses of every
+        system's diagonal blocks of ``block_size`` rows, 1..8, formed on the
+        device at each solve from the values that solve reads) or ``Given``
+        with ``blocks``, an (nsys, n, block_size) or (nsys, n * block_size)
+        array, row i of system s holding row i of its block's matrix; it is
+        uploaded and kept alive by the object. Each block symmetric positive
+        definite is the caller's duty. A system with a bad block stops alone
+        with code 3 and its x untouched. It replaces a preconditioner set by
+        ``set_preconditioner`` and is replaced by it. ValueError, before any
+        device call, for an unknown kind, a block size outside 1..8, missing
+        ``blocks`` or a wrong shape."""
+        try:
+            kind = BlockPreconditioner(kind)
+        except (ValueError, TypeError):
+            raise ValueError(f"unknown block preconditioner kind {kind!r}") from None
+        bs, d_w = 0, None
+        if kind != BlockPreconditioner.None_:
+            bs = int(block_size)
+            if not 1 <= bs <= MAX_BLOCK_SIZE:
+                raise ValueError(f"block_size {block_size!r} must be 1..{MAX_BLOCK_SIZE}")
+        if kind == BlockPreconditioner.Given:
+            if blocks is None:
+                raise ValueError("BlockPreconditioner.Given needs blocks, an (nsys, n, "
+                                 "block_size) array")
+            arr = np.asarray(blocks, dtype=np.float64)
+            if arr.shape not in ((self.nsys, self.n, bs), (self.nsys, self.n * bs)):
+                raise ValueError(f"blocks has shape {arr.shape}, expected "
+                                 f"{(self.nsys, self.n, bs)} or {(self.nsys, self.n * bs)}")
+            d_w = DeviceArray(self._queue, self.nsys * self.n * bs, np.float64).upload(arr.ravel())
+        check(lib().cgx_many_set_block_precond(self._h, int(kind), bs,
+                                               d_w.ptr if d_w else None, self.n * bs))
+        self._block, self._blocks = kind, d_w  # (the old blocks live until the call above)
+        self._precond, self._diag = Preconditioner.None_, None  # replaced
+        self.rz = None
+
+    def block_inv(self, block_size: int):
+        """(W, bad_systems): W (nsys, n, block_size), the inverses of every
+        system's diagonal blocks as ``set_block_preconditioner(Jacobi)`` forms
+        them from the current values (cgx_many_block_inv; the columns past a
+        partial last block are 0), and the indices of the systems with a block
+        whose pivot is not positive and finite. ValueError, before any device
+        call, for a block size outside 1..8."""
+        bs = int(block_size)
+        if not 1 <= bs <= MAX_BLOCK_SIZE:
+            raise ValueError(f"block_size {block_size!r} must be 1..{MAX_BLOCK_SIZE}")
+        ns, n = self.nsys, self.n
+        out = DeviceArray(self._queue, ns * n * bs, np.float64)
+        nbad, first = C.c_int64(0), C.c_int64(-1)
+        check(lib().cgx_many_block_inv(self._h, bs, out.ptr, n * bs, C.byref(nbad),
+                                       C.byref(first)))
+        verdicts = (C.c_int * ns)()
+        check(lib().cgx_many_block_bad(self._h, verdicts))
+        bad = np.nonzero(np.array(verdicts[:]))[0]  # (nbad of them, the first one `first`)
+        return out.download()[:ns * n * bs].reshape(ns, n, bs), bad
 
     def solve(self, B, X0=None, improvement: float = 0.0, max_iter: int = -1) -> np.ndarray:
         """Solve A_s x_s = b_s for every s: ``B`` (nsys, n), ``X0`` the initial
@@ -909,7 +970,8 @@ class ManyCG:
         self.rxr = np.array(rxr[:], dtype=np.float64)
         self.stopped = np.array(stopped[:], dtype=np.int32)
         self.rz = None
-        if getattr(self, "_precond", Preconditioner.None_) != Preconditioner.None_:
+        if getattr(self, "_precond", Preconditioner.None_) != Preconditioner.None_ or \
+                getattr(self, "_block", BlockPreconditioner.None_) != BlockPreconditioner.None_:
             rz = (C.c_double * ns)()
             check(lib().cgx_many_rz(self._h, rz))
             self.rz = np.array(rz[:], dtype=np.float64)

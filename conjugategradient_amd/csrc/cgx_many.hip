@@ -12,15 +12,19 @@
 // before adds (-ffp-contract=off), a row summed by one thread from 0 in
 // ascending entry order, the dots double-length sums (cgx_dd.h) rounded once,
 // stop rule Q5 as k_update_xp applies it. With cgx_many_set_precond the same
-// kernel runs PCG with a diagonal M^-1 (k_many_cg's PC), pinned the same way
+// kernel runs PCG with a diagonal M^-1 (kManyDiag), pinned the same way
 // to mode 1 under cgx_cg_set_precond. For n <= 256 k_many_cg_wave gives each
 // system a wave instead (cgx_many_set_form): the same arithmetic, four
-// independent solves per workgroup and no workgroup barrier.
+// independent solves per workgroup and no workgroup barrier. With
+// cgx_many_set_block_precond both forms run PCG with dense diagonal blocks of
+// 1 to 8 rows (kManyBlock), pinned to mode 1 under cgx_cg_set_block_precond;
+// the blocks' inverses come from a launch of their own (k_many_block_inv).
 #include <cmath>
 #include <climits>
 #include <limits>
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 #include "cgx_dd.h"
 #include "cgx_objects.h"
@@ -45,10 +49,23 @@ struct ManyArgs {
   int *stopped;
   double tol;
   int nsys, n, cap;
+  int bs;  // the block form's block size (in what was padding: every other argument stays
+           // where it was, and so does the size)
   // the preconditioned form's (last: the plain form's arguments stay where they were)
-  const double *M;  // DIAGONAL: the caller's m, system s at M + s ldm; JACOBI: NULL
+  const double *M;  // DIAGONAL: the caller's m, system s at M + s ldm; JACOBI: NULL; the
+                    // block form: W, system s's n x bs inverse blocks at M + s ldm
   int64_t ldm;
   double *rz;       // per system: r.z after the last body
+};
+// The block form's verdict on a system is its word of `stopped`: zeroed before
+// the launches of a solve, set to not 0 by the fill or the check where a block
+// is bad, read by the CG kernel when it takes the system.
+
+// what a CG kernel does with the residual before it enters p
+enum ManyPc {
+  kManyPlain = 0,  // nothing: CG
+  kManyDiag = 1,   // z = m o r (cgx_many_set_precond)
+  kManyBlock = 2   // z = blockdiag(W_b) r (cgx_many_set_block_precond)
 };
 
 // k_diag_inv's verdict on a diagonal (or on a caller's m): positive and finite
@@ -98,10 +115,77 @@ __device__ __forceinline__ void many_sum2(Dd<double> u, Dd<double> v, double *re
   *sv = z.value();
 }
 
+// z_i = sum_j w[j] rs[b0 + j] over the block's real columns: from +0.0 in
+// ascending j, each product rounded before its add (k_pc_init_blk,
+// update_r_blk_body). w: the row's BS values of W; rs: the system's r in LDS;
+// b0 the block's first row. All BS loads of w are issued before the first
+// add, with no branch between them. In a partial last block rs is read up to
+// BS - 1 doubles past row n - 1, at most kManyStagePad past the staged rows
+// (LDS of the kernel's own), and w's +0.0 padding columns: neither is added.
+constexpr int kManyStagePad = 8;
+template <int BS>
+__device__ __forceinline__ double many_block_z(const double *__restrict__ w, int b0, int n,
+                                               const double *rs) {
+  const int nc = min(BS, n - b0);  // the block's real columns (BS but in a partial last block)
+  double wv[BS];
+#pragma unroll
+  for (int j = 0; j < BS; ++j) wv[j] = w[j];
+  const double *rb = rs + b0;
+  double z = 0.0;
+#pragma unroll
+  for (int j = 0; j < BS; ++j) {
+    const double t = z + wv[j] * rb[j];
+    z = j < nc ? t : z;
+  }
+  return z;
+}
+
+// z = M^-1 r at a thread's own rows t, t + S, ... (S: kBlock, or kWave in the
+// wave form) from the staged r: z into zk, and into pz where that is not NULL
+// (the init's p); r.z's share into accz. bs is uniform, and so is the switch:
+// each block size has its own unrolled sweep, whose loads sit at constant
+// offsets from the row's one address. That address is formed anew at every
+// use (the empty asm hides that it never changes): kept across the body loop
+// the rows' addresses would push x, r and z out of the registers.
+// A row's block starts at floor(i / bs) bs: for i < 4,096 and bs <= 8
+// (i + 0.5) / bs lies at least 1 / 16 from an integer, far beyond a float's
+// rounding of it, so the truncated float quotient is the integer one.
+template <int R, int S>
+__device__ __forceinline__ void many_block_sweep(const double *__restrict__ Ws, int bs, int t,
+                                                 int n, const double *rs, const double *r,
+                                                 double *zk, Dd<double> &accz, double *pz) {
+  const float inv = 1.0f / (float)bs;
+  auto sweep = [&](auto BS) {
+    constexpr int bsc = decltype(BS)::value;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      int i = t + k * S;
+      if (i < n) {
+        asm volatile("" : "+v"(i));
+        const int b0 = (int)(((float)i + 0.5f) * inv) * bsc;
+        const double z = many_block_z<bsc>(Ws + i * bsc, b0, n, rs);
+        accz += r[k] * z;
+        zk[k] = z;
+        if (pz) pz[i] = z;
+      }
+    }
+  };
+  switch (bs) {
+    case 1: sweep(std::integral_constant<int, 1>()); break;
+    case 2: sweep(std::integral_constant<int, 2>()); break;
+    case 3: sweep(std::integral_constant<int, 3>()); break;
+    case 4: sweep(std::integral_constant<int, 4>()); break;
+    case 5: sweep(std::integral_constant<int, 5>()); break;
+    case 6: sweep(std::integral_constant<int, 6>()); break;
+    case 7: sweep(std::integral_constant<int, 7>()); break;
+    default: sweep(std::integral_constant<int, 8>()); break;
+  }
+}
+
 // R rows per thread: n <= R kBlock. LDS: p (R kBlock doubles) and two
 // reduction stagings.
 //
-// PC: diagonal preconditioning (cgx_many_set_precond), statement for statement
+// kManyDiag: diagonal preconditioning (cgx_many_set_precond), statement for statement
 // as k_pc_init, update_r_pc_body, k_update_xp_pc and pc_stop_rule
 // (cgx_kernels.hip): z_i = m_i * r_i, rounded, never stored beyond the body
 // that forms it (it takes Ap's register once r is updated); alpha = rz / p.Ap,
@@ -117,16 +201,32 @@ __device__ __forceinline__ void many_sum2(Dd<double> u, Dd<double> v, double *re
 // written: X as given, 0 bodies, NaN r.r and r.z, stop code 3. `refused`
 // carries the verdict across the init's first barrier; the extra barrier of
 // that path keeps a thread that is already at the next system from writing
-// the word while another still reads it. The plain form (PC = false) is the
-// code it was: every addition is behind `if constexpr (PC)`.
-template <int R, bool PC>
+// the word while another still reads it. The plain form (kManyPlain) is the
+// code it was: every addition is behind `if constexpr`.
+//
+// kManyBlock: block-Jacobi preconditioning (cgx_many_set_block_precond),
+// statement for statement as k_pc_init_blk and update_r_blk_body. A block's
+// rows belong to different threads (a block across a multiple of kBlock wraps
+// from thread 255 to thread 0), so the updated r goes through LDS: mm is the
+// r staging here (there is no m), published by the barrier of the r.r sum;
+// each thread then forms z for its own rows from its row of W_s (bs
+// contiguous doubles, read from memory every body) and the block's r, keeps
+// it where Ap was, and r.z is a third sum: four barriers a body. The sums use
+// three stagings, red[0][0..8) for p.Ap, red[1][0..8) for r.r and
+// red[1][8..16) for r.z, each written once a body, so many_sum's rule holds.
+// A bad system's verdict comes from the launch before this one (stopped[s]): its
+// address is uniform, so is the `continue`, and nothing of that system is
+// touched but its four outputs.
+template <int R, ManyPc PC>
 __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
+  constexpr bool DG = PC == kManyDiag, BK = PC == kManyBlock, PCD = PC != kManyPlain;
   __shared__ double p[R * kBlock];
-  __shared__ double red[2][PC ? 16 : 8];
-  __shared__ double mm[PC ? R * kBlock : 1];  // (unused, and dropped, without PC)
-  __shared__ int refused;                     // (the same)
+  __shared__ double red[2][PCD ? 16 : 8];
+  // (unused, and dropped, in the plain form; the block form's staged r, read past its end)
+  __shared__ double mm[PCD ? R * kBlock + (BK ? kManyStagePad : 0) : 1];
+  __shared__ int refused;                      // (the same; the diagonal form's alone)
   const int t = threadIdx.x, n = a.n;
-  if constexpr (PC) {
+  if constexpr (DG) {
     if (t == 0) refused = 0;
     __syncthreads();
   }
@@ -142,6 +242,17 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
     const double *__restrict__ val = a.val + (int64_t)s * a.ldv;
     const double *__restrict__ b = a.B + (int64_t)s * a.ldb;
     double *__restrict__ xs = a.X + (int64_t)s * a.ldx;
+    if constexpr (BK) {
+      if (a.stopped[s] != 0) {  // the verdict; uniform: one address for the workgroup
+        if (t == 0) {
+          a.bodies[s] = 0;
+          a.rxr[s] = __builtin_nan("");
+          a.rz[s] = __builtin_nan("");
+          a.stopped[s] = 3;
+        }
+        continue;
+      }
+    }
     double x[R], r[R];
     // ---- init: r = b - A x, p = r, rxr = r.r (k_cg_init) ----
 #pragma unroll
@@ -150,7 +261,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
       x[k] = i < n ? xs[i] : 0.0;
       if (i < n) p[i] = x[k];  // x through LDS: the init's gather source
     }
-    if constexpr (PC) {  // m of the own rows, and the verdict on it
+    if constexpr (DG) {  // m of the own rows, and the verdict on it
       bool bad = false;
 #pragma unroll
       for (int k = 0; k < R; ++k) {
@@ -177,7 +288,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
       if (bad) refused = s + 1;  // (s + 1 > 0 marks this system alone: no reset)
     }
     __syncthreads();
-    if constexpr (PC) {
+    if constexpr (DG) {
       if (refused == s + 1) {  // uniform: every thread reads it behind the barrier
         if (t == 0) {
           a.bodies[s] = 0;
@@ -199,11 +310,17 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
       if (i < n) {
         r[k] = b[i] - sum;
         acc += r[k] * r[k];
+        if constexpr (BK) mm[i] = r[k];  // staged for the blocks' other rows
       }
     }
     __syncthreads();  // every gather of x is done: p may be overwritten
     double rxr, rz = 0.0;
-    if constexpr (PC) {  // p = m o r, rz = r.(m o r) (k_pc_init)
+    if constexpr (BK) {  // p = z = M^-1 r, rz = r.z (k_pc_init_blk)
+      Dd<double> accz(0.0);
+      double z0[R];
+      many_block_sweep<R, kBlock>(a.M + (int64_t)s * a.ldm, a.bs, t, n, mm, r, z0, accz, p);
+      many_sum2(acc, accz, red[1], &rxr, &rz);  // (its barrier publishes p too)
+    } else if constexpr (DG) {  // p = m o r, rz = r.(m o r) (k_pc_init)
       Dd<double> accz(0.0);
 #pragma unroll
       for (int k = 0; k < R; ++k) {
@@ -239,12 +356,27 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
         if (i < n) acc += sum * p[i];
       }
       const double pAp = many_sum(acc, red[0]);
-      const double alpha = (PC ? rz : rxr) / pAp;
+      const double alpha = (PCD ? rz : rxr) / pAp;
       // r -= alpha Ap and r.r (k_update_r); PC: r.z in the same sweep, z
       // kept where Ap was (update_r_pc_body)
       acc = Dd<double>(0.0);
       double rr, rzn = 0.0;
-      if constexpr (PC) {
+      if constexpr (BK) {  // (update_r_blk_body)
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+          const int i = t + k * kBlock;
+          if (i < n) {
+            r[k] = r[k] - alpha * Ap[k];
+            acc += r[k] * r[k];
+            mm[i] = r[k];
+          }
+        }
+        rr = many_sum(acc, red[1]);  // (its barrier publishes the staged r too)
+        Dd<double> accz(0.0);
+        many_block_sweep<R, kBlock>(a.M + (int64_t)s * a.ldm, a.bs, t, n, mm, r, Ap, accz,
+                                    nullptr);
+        rzn = many_sum(accz, red[1] + 8);
+      } else if constexpr (DG) {
         Dd<double> accz(0.0);
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -269,7 +401,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
         }
         rr = many_sum(acc, red[1]);
       }
-      const double beta = PC ? rzn / rz : rr / rxr;
+      const double beta = PCD ? rzn / rz : rr / rxr;
       // x += alpha p; p = r + beta p (PC: m o r + beta p); the stop rule
       // (k_update_xp, k_update_xp_pc). Every gather of this body's p lies
       // before the two barriers above.
@@ -279,7 +411,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
         if (i < n) {
           const double pv = p[i];
           x[k] = x[k] + alpha * pv;
-          p[i] = (PC ? Ap[k] : r[k]) + beta * pv;
+          p[i] = (PCD ? Ap[k] : r[k]) + beta * pv;
         }
       }
       ++bodies;
@@ -287,7 +419,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
       const bool cont = !cond && bodies < a.cap;
       stopped = cond ? 1 : (cont ? 0 : 2);
       rxr = rr;
-      if constexpr (PC) rz = rzn;
+      if constexpr (PCD) rz = rzn;
       __syncthreads();  // the new p, before the next gather (or the next system's x)
       if (!cont) break;
     }
@@ -300,7 +432,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
       a.bodies[s] = bodies;
       a.rxr[s] = rxr;
       a.stopped[s] = stopped;
-      if constexpr (PC) a.rz[s] = rz;
+      if constexpr (PCD) a.rz[s] = rz;
     }
   }
 }
@@ -336,19 +468,21 @@ __device__ __forceinline__ double wave_dot(Dd<double> v) {
 
 // R rows per lane: n <= R kWave. Wave w of workgroup b runs systems 4 b + w,
 // 4 b + w + 4 grid, ...; lane l owns rows l, l + 64, ...: their x and r in
-// registers, p (and m under PC) in the wave's own R kWave doubles of LDS. The
+// registers, p (and m, or the block form's staged r) in the wave's own LDS. The
 // four waves of a workgroup never meet: there is no workgroup barrier below
 // (they run different body counts, so one would hang), only wave_order()
 // where k_many_cg has a barrier. The arithmetic is k_many_cg's, statement for
 // statement; a bad diagonal's verdict is a wave vote.
-template <int R, bool PC>
+template <int R, ManyPc PC>
 __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
+  constexpr bool DG = PC == kManyDiag, BK = PC == kManyBlock, PCD = PC != kManyPlain;
   __shared__ double p_all[kWaves * R * kWave];
-  __shared__ double m_all[PC ? kWaves * R * kWave : 1];  // (unused, and dropped, without PC)
+  // (unused, and dropped, in the plain form; the block form's staged r, read past its end)
+  __shared__ double m_all[PCD ? kWaves * R * kWave + (BK ? kManyStagePad : 0) : 1];
   const int lane = threadIdx.x & (kWave - 1), n = a.n;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   double *const p = p_all + w * (R * kWave);
-  [[maybe_unused]] double *const mm = m_all + (PC ? w * (R * kWave) : 0);
+  [[maybe_unused]] double *const mm = m_all + (PCD ? w * (R * kWave) : 0);
   // the pattern is every system's: a lane's row bounds stay in registers
   int e0[R], e1[R];
 #pragma unroll
@@ -361,6 +495,17 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
     const double *__restrict__ val = a.val + (int64_t)s * a.ldv;
     const double *__restrict__ b = a.B + (int64_t)s * a.ldb;
     double *__restrict__ xs = a.X + (int64_t)s * a.ldx;
+    if constexpr (BK) {
+      if (a.stopped[s] != 0) {  // the verdict; uniform: one address for the wave
+        if (lane == 0) {
+          a.bodies[s] = 0;
+          a.rxr[s] = __builtin_nan("");
+          a.rz[s] = __builtin_nan("");
+          a.stopped[s] = 3;
+        }
+        continue;
+      }
+    }
     double x[R], r[R];
     // ---- init: r = b - A x, p = r, rxr = r.r (k_cg_init) ----
 #pragma unroll
@@ -369,7 +514,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
       x[k] = i < n ? xs[i] : 0.0;
       if (i < n) p[i] = x[k];  // x through LDS: the init's gather source
     }
-    if constexpr (PC) {  // m of the own rows, and the verdict on it
+    if constexpr (DG) {  // m of the own rows, and the verdict on it
       bool bad = false;
 #pragma unroll
       for (int k = 0; k < R; ++k) {
@@ -414,11 +559,18 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
       if (i < n) {
         r[k] = b[i] - sum;
         acc += r[k] * r[k];
+        if constexpr (BK) mm[i] = r[k];  // staged for the blocks' other rows
       }
     }
     wave_order();  // every gather of x is done: p may be overwritten
     double rxr, rz = 0.0;
-    if constexpr (PC) {  // p = m o r, rz = r.(m o r) (k_pc_init)
+    if constexpr (BK) {  // p = z = M^-1 r, rz = r.z (k_pc_init_blk)
+      Dd<double> accz(0.0);
+      double z0[R];
+      many_block_sweep<R, kWave>(a.M + (int64_t)s * a.ldm, a.bs, lane, n, mm, r, z0, accz, p);
+      rxr = wave_dot(acc);
+      rz = wave_dot(accz);
+    } else if constexpr (DG) {  // p = m o r, rz = r.(m o r) (k_pc_init)
       Dd<double> accz(0.0);
 #pragma unroll
       for (int k = 0; k < R; ++k) {
@@ -456,12 +608,28 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
         if (i < n) acc += sum * p[i];
       }
       const double pAp = wave_dot(acc);
-      const double alpha = (PC ? rz : rxr) / pAp;
+      const double alpha = (PCD ? rz : rxr) / pAp;
       // r -= alpha Ap and r.r (k_update_r); PC: r.z in the same sweep, z
       // kept where Ap was (update_r_pc_body)
       acc = Dd<double>(0.0);
       double rr, rzn = 0.0;
-      if constexpr (PC) {
+      if constexpr (BK) {  // (update_r_blk_body)
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+          const int i = lane + k * kWave;
+          if (i < n) {
+            r[k] = r[k] - alpha * Ap[k];
+            acc += r[k] * r[k];
+            mm[i] = r[k];
+          }
+        }
+        wave_order();  // the staged r is written
+        Dd<double> accz(0.0);
+        many_block_sweep<R, kWave>(a.M + (int64_t)s * a.ldm, a.bs, lane, n, mm, r, Ap, accz,
+                                   nullptr);
+        rr = wave_dot(acc);
+        rzn = wave_dot(accz);
+      } else if constexpr (DG) {
         Dd<double> accz(0.0);
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -487,7 +655,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
         }
         rr = wave_dot(acc);
       }
-      const double beta = PC ? rzn / rz : rr / rxr;
+      const double beta = PCD ? rzn / rz : rr / rxr;
       wave_order();  // every gather of this body's p is done
       // x += alpha p; p = r + beta p (PC: m o r + beta p); the stop rule
       // (k_update_xp, k_update_xp_pc)
@@ -497,7 +665,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
         if (i < n) {
           const double pv = p[i];
           x[k] = x[k] + alpha * pv;
-          p[i] = (PC ? Ap[k] : r[k]) + beta * pv;
+          p[i] = (PCD ? Ap[k] : r[k]) + beta * pv;
         }
       }
       ++bodies;
@@ -505,7 +673,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
       const bool cont = !cond && bodies < a.cap;
       stopped = cond ? 1 : (cont ? 0 : 2);
       rxr = rr;
-      if constexpr (PC) rz = rzn;
+      if constexpr (PCD) rz = rzn;
       wave_order();  // the new p, before the next gather (or the next system's x)
       if (!cont) break;
     }
@@ -518,7 +686,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
       a.bodies[s] = bodies;
       a.rxr[s] = rxr;
       a.stopped[s] = stopped;
-      if constexpr (PC) a.rz[s] = rz;
+      if constexpr (PCD) a.rz[s] = rz;
     }
   }
 }
@@ -547,13 +715,130 @@ __global__ __launch_bounds__(kBlock) void k_many_check(int n, int nnz,
   if (bc) atomicAdd(&bad[1], bc);
 }
 
+// ---- block-Jacobi: the blocks' inverses (cgx_many_set_block_precond) -------
+// W_b = (diagonal block b of A_s)^-1 for every system s and block b, one thread
+// per (system, block): k_block_inv's statements (cgx_kernels.hip) restated,
+// which follow tests/bj_model.py block_inverse and csr_blocks one by one. Row
+// i of a block takes the entries of CSR row i with b0 <= col <= i (the lower
+// triangle decides; duplicates summed from 0 in entry order; rows may be
+// unsorted); LDL^T without pivoting; W = M^T D^-1 M with M = L^-1, the lower
+// triangle computed and mirrored; the columns past a partial last block +0.0.
+// System s's W is n x BS row-major at out + s ldw; [n BS, ldw) is not written.
+// A pivot that is not positive and finite (many_pc_ok) marks the system:
+// bad[s] = 1, atomically, and the block's W holds whatever the statements give.
+template <int BS>
+__global__ __launch_bounds__(kBlock) void k_many_block_inv(int nsys, int n,
+                                                           const int *__restrict__ rowptr,
+                                                           const int *__restrict__ col,
+                                                           const double *__restrict__ vals,
+                                                           int64_t ldv, double *__restrict__ outs,
+                                                           int64_t ldw, int *bad) {
+  const int nb = (n + BS - 1) / BS;
+  const int64_t items = (int64_t)nsys * nb, stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t it = (int64_t)blockIdx.x * kBlock + threadIdx.x; it < items; it += stride) {
+    const int s = (int)(it / nb);
+    const int b0 = (int)(it - (int64_t)s * nb) * BS;
+    const double *__restrict__ val = vals + (int64_t)s * ldv;
+    double *__restrict__ out = outs + (int64_t)s * ldw;
+    const int m = min(BS, n - b0);  // rows of this block
+    double B[BS][BS], L[BS][BS], M[BS][BS], D[BS], E[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+#pragma unroll
+      for (int j = 0; j <= i; ++j) B[i][j] = 0.0;
+      if (i < m) {
+        for (int k = rowptr[b0 + i]; k < rowptr[b0 + i + 1]; ++k) {
+          const int c = col[k] - b0;
+          const double v = val[k];
+#pragma unroll
+          for (int j = 0; j <= i; ++j)
+            if (c == j) B[i][j] = B[i][j] + v;
+        }
+      }
+    }
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < BS; ++j) {
+      if (j < m) {
+        double sj = B[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) sj = sj - L[j][k] * (L[j][k] * D[k]);
+        D[j] = sj;
+        if (!many_pc_ok(sj)) ok = false;
+#pragma unroll
+        for (int i = j + 1; i < BS; ++i) {
+          if (i < m) {
+            double tj = B[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) tj = tj - L[i][k] * (L[j][k] * D[k]);
+            L[i][j] = tj / sj;
+          }
+        }
+        E[j] = 1.0 / sj;
+      }
+    }
+    // M = L^-1 (unit lower triangle): M[i][j] = -(L[i][j] + sum_{j<k<i} L[i][k] M[k][j])
+#pragma unroll
+    for (int i = 1; i < BS; ++i) {
+      if (i < m) {
+#pragma unroll
+        for (int j = 0; j < i; ++j) {
+          double sj = L[i][j];
+#pragma unroll
+          for (int k = j + 1; k < i; ++k) sj = sj + L[i][k] * M[k][j];
+          M[i][j] = -sj;
+        }
+      }
+    }
+    // W = M^T D^-1 M, the lower triangle computed and mirrored
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+      if (i < m) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+          double sj = j == i ? E[i] : M[i][j] * E[i];
+#pragma unroll
+          for (int k = i + 1; k < BS; ++k)
+            if (k < m) sj = sj + (M[k][i] * E[k]) * (j == i ? M[k][i] : M[k][j]);
+          out[(b0 + i) * BS + j] = sj;
+          out[(b0 + j) * BS + i] = sj;
+        }
+#pragma unroll
+        for (int j = 0; j < BS; ++j)
+          if (j >= m) out[(b0 + i) * BS + j] = 0.0;
+      }
+    }
+    if (!ok) atomicOr(&bad[s], 1);
+  }
+}
+
+// A caller's W (CGX_BLOCK_GIVEN), one thread per (system, row), as
+// k_block_check: every entry of a real column finite, W_b[i, i] positive and
+// finite; a row that fails marks its system, bad[s] = 1, atomically.
+__global__ __launch_bounds__(kBlock) void k_many_block_check(int nsys, int n, int bs,
+                                                             const double *__restrict__ Ws,
+                                                             int64_t ldw, int *bad) {
+  const int64_t items = (int64_t)nsys * n, stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t it = (int64_t)blockIdx.x * kBlock + threadIdx.x; it < items; it += stride) {
+    const int s = (int)(it / n);
+    const int i = (int)(it - (int64_t)s * n);
+    const double *__restrict__ w = Ws + (int64_t)s * ldw + (int64_t)i * bs;
+    const int b0 = (i / bs) * bs;
+    const int nc = min(bs, n - b0);
+    bool ok = many_pc_ok(w[i - b0]);
+    for (int j = 0; j < nc; ++j)
+      if (!(fabs(w[j]) <= std::numeric_limits<double>::max())) ok = false;  // NaN, Inf
+    if (!ok) atomicOr(&bad[s], 1);
+  }
+}
+
 int many_rows_per_thread(int64_t n) {
   int r = 1;
   while ((int64_t)r * kBlock < n) r *= 2;
   return r;
 }
 
-template <bool PC> const void *many_kernel_of(int r) {
+template <ManyPc PC> const void *many_kernel_of(int r) {
   switch (r) {
     case 1: return reinterpret_cast<const void *>(&k_many_cg<1, PC>);
     case 2: return reinterpret_cast<const void *>(&k_many_cg<2, PC>);
@@ -570,7 +855,7 @@ int many_rows_per_lane(int64_t n) {  // the wave form's R (n <= kManyWaveMaxN)
   return r;
 }
 
-template <bool PC> const void *many_wave_kernel_of(int r) {
+template <ManyPc PC> const void *many_wave_kernel_of(int r) {
   switch (r) {
     case 1: return reinterpret_cast<const void *>(&k_many_cg_wave<1, PC>);
     case 2: return reinterpret_cast<const void *>(&k_many_cg_wave<2, PC>);
@@ -579,21 +864,26 @@ template <bool PC> const void *many_wave_kernel_of(int r) {
   }
 }
 
-const void *many_kernel(int r, bool pc, bool wave) {
-  if (wave) return pc ? many_wave_kernel_of<true>(r) : many_wave_kernel_of<false>(r);
-  return pc ? many_kernel_of<true>(r) : many_kernel_of<false>(r);
+const void *many_kernel(int r, ManyPc pc, bool wave) {
+  if (wave)
+    return pc == kManyBlock  ? many_wave_kernel_of<kManyBlock>(r)
+           : pc == kManyDiag ? many_wave_kernel_of<kManyDiag>(r)
+                             : many_wave_kernel_of<kManyPlain>(r);
+  return pc == kManyBlock  ? many_kernel_of<kManyBlock>(r)
+         : pc == kManyDiag ? many_kernel_of<kManyDiag>(r)
+                           : many_kernel_of<kManyPlain>(r);
 }
 
 // workgroups of k_many_cg<r, pc> (wave: k_many_cg_wave<r, pc>) resident on the
 // device at once (occupancy x CUs; 0: unknown), as spmv_dot_resident
-int many_resident(int r, bool pc, bool wave) {
+int many_resident(int r, ManyPc pc, bool wave) {
   static std::mutex mu;
-  // (device, 4 r + 2 with the wave form + 1 with pc) -> workgroups
+  // (device, 8 r + 4 with the wave form + pc) -> workgroups
   static std::map<std::pair<int, int>, int> cache;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   std::lock_guard<std::mutex> lk(mu);
-  const std::pair<int, int> key{dev, 4 * r + (wave ? 2 : 0) + (pc ? 1 : 0)};
+  const std::pair<int, int> key{dev, 8 * r + (wave ? 4 : 0) + (int)pc};
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
   int res = 0, nb = 0, cus = 0;
@@ -618,6 +908,12 @@ struct cgx_many {
   int precond = CGX_PRECOND_NONE;  // cgx_many_set_precond: the next solve's
   const double *d_M = nullptr;     // DIAGONAL: the caller's
   int64_t ldm = 0;
+  // cgx_many_set_block_precond (excludes the diagonal one: at most one is set)
+  int blk_kind = CGX_BLOCK_NONE, blk_bs = 0;
+  const double *d_W = nullptr;  // GIVEN: the caller's
+  int64_t ldw = 0;
+  double *d_Wown = nullptr;     // JACOBI: nsys x n blk_bs, refilled by every solve
+  bool bad_valid = false;       // h_stopped holds the last cgx_many_block_inv's verdicts
   bool rz_valid = false;  // the last solve was preconditioned, with this preconditioner
   long long *d_bodies = nullptr;
   double *d_rxr = nullptr, *d_rz = nullptr;
@@ -631,7 +927,7 @@ namespace {
 
 void many_free(cgx_many *m) {
   if (!m) return;
-  void *dev[] = {m->d_bodies, m->d_rxr, m->d_rz, m->d_stopped};
+  void *dev[] = {m->d_bodies, m->d_rxr, m->d_rz, m->d_stopped, m->d_Wown};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   void *host[] = {m->h_bodies, m->h_rxr, m->h_rz, m->h_stopped};
@@ -641,7 +937,13 @@ void many_free(cgx_many *m) {
   delete m;
 }
 
-template <bool PC>
+// what the next solve's kernel does with r
+ManyPc many_pc(const cgx_many *m) {
+  if (m->blk_kind != CGX_BLOCK_NONE) return kManyBlock;
+  return m->precond != CGX_PRECOND_NONE ? kManyDiag : kManyPlain;
+}
+
+template <ManyPc PC>
 void many_launch(int r, dim3 grid, dim3 block, hipStream_t s, const ManyArgs &a) {
   switch (r) {
     case 1: hipLaunchKernelGGL((k_many_cg<1, PC>), grid, block, 0, s, a); break;
@@ -652,7 +954,7 @@ void many_launch(int r, dim3 grid, dim3 block, hipStream_t s, const ManyArgs &a)
   }
 }
 
-template <bool PC>
+template <ManyPc PC>
 void many_launch_wave(int r, dim3 grid, dim3 block, hipStream_t s, const ManyArgs &a) {
   switch (r) {
     case 1: hipLaunchKernelGGL((k_many_cg_wave<1, PC>), grid, block, 0, s, a); break;
@@ -676,10 +978,52 @@ int many_rows(const cgx_many *m) {
   return many_form(m) == CGX_MANY_FORM_WAVE ? many_rows_per_lane(m->n) : m->r;
 }
 
+// back to no block preconditioner; its workspace goes
+void many_drop_block(cgx_many *m) {
+  if (m->d_Wown) {
+    (void)hipStreamSynchronize(m->ctx->stream);
+    (void)hipFree(m->d_Wown);
+    m->d_Wown = nullptr;
+  }
+  m->blk_kind = CGX_BLOCK_NONE;
+  m->blk_bs = 0;
+  m->d_W = nullptr;
+  m->ldw = 0;
+}
+
+int many_elem_grid(int64_t items) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>((items + kBlock - 1) / kBlock, kMaxGrid));
+}
+
+// every system's W into out (system s at out + s ldw), bad[s] set where a block is bad
+hipError_t many_block_fill(const cgx_many *m, int bs, double *out, int64_t ldw, int *bad,
+                           hipStream_t s) {
+  const int n = (int)m->n, nsys = (int)m->nsys;
+  const dim3 grid(many_elem_grid((int64_t)nsys * ((n + bs - 1) / bs))), block(kBlock);
+#define CGX_MANY_BINV(BS)                                                                    \
+  case BS:                                                                                   \
+    hipLaunchKernelGGL(k_many_block_inv<BS>, grid, block, 0, s, nsys, n, m->rowptr, m->col,  \
+                       m->val, m->ldv, out, ldw, bad);                                       \
+    break
+  switch (bs) {
+    CGX_MANY_BINV(1);
+    CGX_MANY_BINV(2);
+    CGX_MANY_BINV(3);
+    CGX_MANY_BINV(4);
+    CGX_MANY_BINV(5);
+    CGX_MANY_BINV(6);
+    CGX_MANY_BINV(7);
+    CGX_MANY_BINV(8);
+    default: return hipErrorInvalidValue;
+  }
+#undef CGX_MANY_BINV
+  return hipGetLastError();
+}
+
 int many_grid(const cgx_many *m) {
   const bool wave = many_form(m) == CGX_MANY_FORM_WAVE;
   int64_t g = wave ? (m->nsys + kWaves - 1) / kWaves : m->nsys;
-  const int res = many_resident(many_rows(m), m->precond != CGX_PRECOND_NONE, wave);
+  const int res = many_resident(many_rows(m), many_pc(m), wave);
   if (res > 0) g = std::min<int64_t>(g, res);
   if (m->max_workgroups > 0) g = std::min<int64_t>(g, m->max_workgroups);
   return (int)std::min<int64_t>(std::max<int64_t>(g, 1), INT_MAX);
@@ -825,18 +1169,37 @@ extern "C" int cgx_many_solve(cgx_many *m, const void *d_B, int64_t ldb, void *d
   a.nsys = (int)m->nsys;
   a.n = (int)n;
   a.cap = (int)cap;
-  const bool pc = m->precond != CGX_PRECOND_NONE;
+  const ManyPc kind = many_pc(m);
+  const bool pc = kind != kManyPlain;
   a.M = m->precond == CGX_PRECOND_DIAGONAL ? m->d_M : nullptr;
   a.ldm = m->ldm;
   a.rz = m->d_rz;
+  a.bs = m->blk_bs;
   m->rz_valid = false;
+  m->bad_valid = false;
+  if (kind == kManyBlock) {  // the verdicts, and under JACOBI this solve's W, in launches before
+    CGX_HIP(hipMemsetAsync(m->d_stopped, 0, (size_t)m->nsys * sizeof(int), s));
+    if (m->blk_kind == CGX_BLOCK_JACOBI) {
+      a.M = m->d_Wown;
+      a.ldm = n * m->blk_bs;
+      CGX_HIP(many_block_fill(m, m->blk_bs, m->d_Wown, a.ldm, m->d_stopped, s));
+    } else {
+      a.M = m->d_W;
+      a.ldm = m->ldw;
+      hipLaunchKernelGGL(k_many_block_check, dim3(many_elem_grid(m->nsys * n)), dim3(kBlock), 0,
+                         s, (int)m->nsys, (int)n, m->blk_bs, m->d_W, m->ldw, m->d_stopped);
+      CGX_HIP(hipGetLastError());
+    }
+  }
   const dim3 grid(many_grid(m)), block(kBlock);
   if (many_form(m) == CGX_MANY_FORM_WAVE) {
-    if (pc) many_launch_wave<true>(many_rows(m), grid, block, s, a);
-    else many_launch_wave<false>(many_rows(m), grid, block, s, a);
+    if (kind == kManyBlock) many_launch_wave<kManyBlock>(many_rows(m), grid, block, s, a);
+    else if (pc) many_launch_wave<kManyDiag>(many_rows(m), grid, block, s, a);
+    else many_launch_wave<kManyPlain>(many_rows(m), grid, block, s, a);
   } else {
-    if (pc) many_launch<true>(m->r, grid, block, s, a);
-    else many_launch<false>(m->r, grid, block, s, a);
+    if (kind == kManyBlock) many_launch<kManyBlock>(m->r, grid, block, s, a);
+    else if (pc) many_launch<kManyDiag>(m->r, grid, block, s, a);
+    else many_launch<kManyPlain>(m->r, grid, block, s, a);
   }
   CGX_HIP(hipGetLastError());
   const size_t ns = (size_t)m->nsys;
@@ -867,10 +1230,107 @@ extern "C" int cgx_many_set_precond(cgx_many *m, int kind, const void *d_M, int6
   if (kind == CGX_PRECOND_DIAGONAL)
     CGX_REQUIRE(ldm >= m->n, CGX_EINVAL, "cgx_many_set_precond: ldm %lld is below n %lld",
                 (long long)ldm, (long long)m->n);
+  if (m->blk_kind != CGX_BLOCK_NONE) many_drop_block(m);  // either call replaces the other's
   m->precond = kind;
   m->d_M = kind == CGX_PRECOND_DIAGONAL ? (const double *)d_M : nullptr;
   m->ldm = kind == CGX_PRECOND_DIAGONAL ? ldm : 0;
   m->rz_valid = false;
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_set_block_precond(cgx_many *m, int kind, int bs, const void *d_W,
+                                          int64_t ldw) {
+  CGX_REQUIRE(kind == CGX_BLOCK_NONE || kind == CGX_BLOCK_JACOBI || kind == CGX_BLOCK_GIVEN,
+              CGX_EINVAL, "cgx_many_set_block_precond: unknown kind %d", kind);
+  if (kind != CGX_BLOCK_NONE)
+    CGX_REQUIRE(bs >= 1 && bs <= 8, CGX_EINVAL,
+                "cgx_many_set_block_precond: block size %d is outside 1..8", bs);
+  if (kind == CGX_BLOCK_GIVEN) {
+    CGX_REQUIRE(d_W, CGX_EINVAL, "cgx_many_set_block_precond: GIVEN needs d_W, which is NULL");
+    CGX_REQUIRE(((uintptr_t)d_W & 7) == 0, CGX_EINVAL,
+                "cgx_many_set_block_precond: d_W must be 8-byte aligned");
+  }
+  CGX_REQUIRE(m, CGX_EINVAL, "cgx_many_set_block_precond: NULL handle");
+  if (kind == CGX_BLOCK_GIVEN)
+    CGX_REQUIRE(ldw >= m->n * bs, CGX_EINVAL,
+                "cgx_many_set_block_precond: ldw %lld is below n * bs = %lld", (long long)ldw,
+                (long long)(m->n * bs));
+  if (kind != CGX_BLOCK_NONE) {
+    DeviceGuard g(m->ctx->device);
+    double *own = nullptr;
+    hipError_t e = hipSuccess;
+    if (kind == CGX_BLOCK_JACOBI &&
+        !(m->blk_kind == CGX_BLOCK_JACOBI && m->blk_bs == bs))  // (else: the one it has)
+      e = hipMalloc((void **)&own, (size_t)m->nsys * (size_t)m->n * bs * sizeof(double));
+    if (e == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      set_error("cgx_many_set_block_precond: out of memory (nsys=%lld, n=%lld, bs=%d)",
+                (long long)m->nsys, (long long)m->n, bs);
+      return CGX_ENOMEM;
+    }
+    if (e != hipSuccess) return hip_fail(e, "cgx_many_set_block_precond");
+    if (own || kind == CGX_BLOCK_GIVEN) {
+      CGX_HIP(hipStreamSynchronize(m->ctx->stream));  // (no solve is in flight: they block)
+      if (m->d_Wown) (void)hipFree(m->d_Wown);
+      m->d_Wown = own;
+    }
+  } else {
+    many_drop_block(m);
+  }
+  m->blk_kind = kind;
+  m->blk_bs = kind == CGX_BLOCK_NONE ? 0 : bs;
+  m->d_W = kind == CGX_BLOCK_GIVEN ? (const double *)d_W : nullptr;
+  m->ldw = kind == CGX_BLOCK_GIVEN ? ldw : 0;
+  m->precond = CGX_PRECOND_NONE;
+  m->d_M = nullptr;
+  m->ldm = 0;
+  m->rz_valid = false;
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_get_block_precond(cgx_many *m, int *kind, int *bs) {
+  CGX_REQUIRE(m, CGX_EINVAL, "cgx_many_get_block_precond: NULL handle");
+  if (kind) *kind = m->blk_kind;
+  if (bs) *bs = m->blk_bs;
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_block_inv(cgx_many *m, int bs, void *d_W, int64_t ldw, int64_t *n_bad,
+                                  int64_t *first_bad) {
+  CGX_REQUIRE(bs >= 1 && bs <= 8, CGX_EINVAL, "cgx_many_block_inv: block size %d is outside 1..8",
+              bs);
+  CGX_REQUIRE(d_W, CGX_EINVAL, "cgx_many_block_inv: d_W is NULL");
+  CGX_REQUIRE(((uintptr_t)d_W & 7) == 0, CGX_EINVAL,
+              "cgx_many_block_inv: d_W must be 8-byte aligned");
+  CGX_REQUIRE(m, CGX_EINVAL, "cgx_many_block_inv: NULL handle");
+  CGX_REQUIRE(ldw >= m->n * bs, CGX_EINVAL,
+              "cgx_many_block_inv: ldw %lld is below n * bs = %lld", (long long)ldw,
+              (long long)(m->n * bs));
+  DeviceGuard g(m->ctx->device);
+  hipStream_t s = m->ctx->stream;
+  const size_t ns = (size_t)m->nsys;
+  m->bad_valid = false;
+  CGX_HIP(hipMemsetAsync(m->d_stopped, 0, ns * sizeof(int), s));  // (a solve's scratch: free here)
+  CGX_HIP(many_block_fill(m, bs, (double *)d_W, ldw, m->d_stopped, s));
+  CGX_HIP(hipMemcpyAsync(m->h_stopped, m->d_stopped, ns * sizeof(int), hipMemcpyDeviceToHost, s));
+  CGX_HIP(hipStreamSynchronize(s));
+  int64_t nbad = 0, first = -1;
+  for (size_t i = 0; i < ns; ++i)
+    if (m->h_stopped[i]) {
+      if (first < 0) first = (int64_t)i;
+      ++nbad;
+    }
+  if (n_bad) *n_bad = nbad;
+  if (first_bad) *first_bad = first;
+  m->bad_valid = true;
+  return CGX_OK;
+}
+
+extern "C" int cgx_many_block_bad(cgx_many *m, int *bad_out) {
+  CGX_REQUIRE(m && bad_out, CGX_EINVAL, "cgx_many_block_bad: NULL argument");
+  CGX_REQUIRE(m->bad_valid, CGX_ESTATE,
+              "cgx_many_block_bad: no cgx_many_block_inv has run since the last solve");
+  for (int64_t i = 0; i < m->nsys; ++i) bad_out[i] = m->h_stopped[i] != 0;
   return CGX_OK;
 }
 
@@ -882,8 +1342,7 @@ extern "C" int cgx_many_get_precond(cgx_many *m, int *kind) {
 
 extern "C" int cgx_many_rz(cgx_many *m, double *rz_out) {
   CGX_REQUIRE(m && rz_out, CGX_EINVAL, "cgx_many_rz: NULL argument");
-  CGX_REQUIRE(m->precond != CGX_PRECOND_NONE, CGX_ESTATE,
-              "cgx_many_rz: no preconditioner is set");
+  CGX_REQUIRE(many_pc(m) != kManyPlain, CGX_ESTATE, "cgx_many_rz: no preconditioner is set");
   CGX_REQUIRE(m->rz_valid, CGX_ESTATE,
               "cgx_many_rz: no solve has run under this preconditioner");
   for (int64_t i = 0; i < m->nsys; ++i) rz_out[i] = m->h_rz[i];
@@ -897,13 +1356,17 @@ extern "C" int cgx_many_info(cgx_many *m, int *workgroups, int *rows_per_thread,
   if (workgroups) *workgroups = many_grid(m);
   if (rows_per_thread) *rows_per_thread = many_rows(m);
   if (lds_bytes) {
-    if (many_form(m) == CGX_MANY_FORM_WAVE)  // four waves' p; preconditioned: their m too
-      *lds_bytes = (int64_t)(m->precond == CGX_PRECOND_NONE ? 1 : 2) * kWaves * many_rows(m) *
-                   kWave * (int64_t)sizeof(double);
-    else  // p and the stagings; preconditioned: m, wider stagings and the verdict word
-      *lds_bytes = m->precond == CGX_PRECOND_NONE
+    const ManyPc pc = many_pc(m);
+    if (many_form(m) == CGX_MANY_FORM_WAVE)  // four waves' p; preconditioned: their m (block
+                                             // form: their staged r) too
+      *lds_bytes = ((int64_t)(pc == kManyPlain ? 1 : 2) * kWaves * many_rows(m) * kWave +
+                    (pc == kManyBlock ? kManyStagePad : 0)) * (int64_t)sizeof(double);
+    else  // p and the stagings; preconditioned: m (block form: the staged r), wider stagings
+          // and, in the diagonal form, the verdict word
+      *lds_bytes = pc == kManyPlain
                        ? ((int64_t)m->r * kBlock + 16) * (int64_t)sizeof(double)
-                       : ((int64_t)2 * m->r * kBlock + 32) * (int64_t)sizeof(double) + 8;
+                       : ((int64_t)2 * m->r * kBlock + 32) * (int64_t)sizeof(double) +
+                             (pc == kManyDiag ? 8 : kManyStagePad * (int64_t)sizeof(double));
   }
   return CGX_OK;
 }

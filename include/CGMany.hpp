@@ -5,7 +5,8 @@
  * An extension: the reference solves one system. A thin C++ layer over the C
  * ABI in the style of the drop-in CG.hpp; double only (CGMany<float> does not
  * compile). Every system's result is the single solve's in mode 1, bit for
- * bit (cgx.h), plain or under setPreconditioner's Jacobi / diagonal.
+ * bit (cgx.h), plain, under setPreconditioner's Jacobi / diagonal or under
+ * setBlockPreconditioner's dense diagonal blocks.
  */
 #ifndef CGSOLVER_CGMANY_HPP
 #define CGSOLVER_CGMANY_HPP
@@ -99,9 +100,68 @@ template <typename DT> class CGMany {
     check(cgx_many_set_precond(_many.get(), kind, d.get(), _n), "cgx_many_set_precond");
     _diag = d;
     _precond = kind;
+    _blocks.reset();  // (replaced)
+    _block = CGX_BLOCK_NONE;
     _final_rz.clear();
   }
   int preconditioner() const { return _precond; }
+
+  /**
+   * The next solves' block preconditioner (cgx_many_set_block_precond): kind
+   * is CGX_BLOCK_NONE, CGX_BLOCK_JACOBI (the inverses of every system's
+   * diagonal blocks of bs rows, 1..8, formed on the device at every solve from
+   * the values that solve reads) or CGX_BLOCK_GIVEN with *blocks, nsys * n * bs
+   * host values: system s's W, n x bs row-major, at blocks[s * n * bs ...], each
+   * block symmetric positive definite (the caller's duty). A system with a bad
+   * block stops alone with code 3, its X untouched. It replaces
+   * setPreconditioner's and is replaced by it.
+   * @throw std::invalid_argument for an unknown kind, bs outside 1..8, missing
+   *        blocks or a wrong length
+   */
+  void setBlockPreconditioner(int kind, int bs, const std::vector<DT> *blocks = nullptr) {
+    if (kind != CGX_BLOCK_NONE && kind != CGX_BLOCK_JACOBI && kind != CGX_BLOCK_GIVEN)
+      throw std::invalid_argument("CGMany::setBlockPreconditioner: unknown kind");
+    if (kind != CGX_BLOCK_NONE && (bs < 1 || bs > 8))
+      throw std::invalid_argument("CGMany::setBlockPreconditioner: bs must be 1..8");
+    std::shared_ptr<void> w;
+    if (kind == CGX_BLOCK_GIVEN) {
+      if (!blocks || (int64_t)blocks->size() != _nsys * _n * bs)
+        throw std::invalid_argument(
+            "CGMany::setBlockPreconditioner: blocks must hold nsys * n * bs entries");
+      w = alloc(blocks->size() * sizeof(DT));
+      check(cgx_h2d(_queue.native(), w.get(), blocks->data(), blocks->size() * sizeof(DT)),
+            "setBlockPreconditioner");
+    }
+    check(cgx_many_set_block_precond(_many.get(), kind, bs, w.get(), _n * bs),
+          "cgx_many_set_block_precond");
+    _blocks = w;
+    _block = kind;
+    _diag.reset();  // (replaced)
+    _precond = CGX_PRECOND_NONE;
+    _final_rz.clear();
+  }
+  int blockPreconditioner() const { return _block; }
+
+  /**
+   * The inverses of every system's diagonal blocks of bs rows as
+   * CGX_BLOCK_JACOBI forms them from the current values (cgx_many_block_inv):
+   * nsys * n * bs values, system s's W at [s * n * bs ...]. *badSystems, when
+   * given, receives the number of systems with a pivot that is not positive
+   * and finite.
+   * @throw std::invalid_argument for bs outside 1..8
+   */
+  std::vector<DT> blockInverse(int bs, int64_t *badSystems = nullptr) {
+    if (bs < 1 || bs > 8) throw std::invalid_argument("CGMany::blockInverse: bs must be 1..8");
+    const size_t len = (size_t)(_nsys * _n * bs);
+    auto w = alloc(len * sizeof(DT));
+    int64_t nbad = 0;
+    check(cgx_many_block_inv(_many.get(), bs, w.get(), _n * bs, &nbad, nullptr),
+          "cgx_many_block_inv");
+    std::vector<DT> out(len);
+    check(cgx_d2h(_queue.native(), out.data(), w.get(), len * sizeof(DT)), "blockInverse");
+    if (badSystems) *badSystems = nbad;
+    return out;
+  }
 
   /**
    * The next solves' kernel form (cgx_many_set_form): CGX_MANY_FORM_AUTO (the
@@ -142,7 +202,7 @@ template <typename DT> class CGMany {
                          _max_iterations, _iterations.data(), _final_rxr.data(), _stopped.data()),
           "cgx_many_solve");
     _final_rz.clear();
-    if (_precond != CGX_PRECOND_NONE) {
+    if (_precond != CGX_PRECOND_NONE || _block != CGX_BLOCK_NONE) {
       _final_rz.assign((size_t)_nsys, 0.0);
       check(cgx_many_rz(_many.get(), _final_rz.data()), "cgx_many_rz");
     }
@@ -170,8 +230,8 @@ template <typename DT> class CGMany {
   acpp::sycl::queue _queue;
   int64_t _nsys = 0, _n = 0, _nnz = 0;
   long long _max_iterations = -1;
-  std::shared_ptr<void> _rows, _cols, _vals, _diag;
-  int _precond = CGX_PRECOND_NONE;
+  std::shared_ptr<void> _rows, _cols, _vals, _diag, _blocks;
+  int _precond = CGX_PRECOND_NONE, _block = CGX_BLOCK_NONE;
   std::shared_ptr<cgx_many> _many;
   std::vector<int64_t> _iterations;
   std::vector<double> _final_rxr, _final_rz;

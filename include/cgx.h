@@ -386,7 +386,8 @@ int cgx_cg_rz(cgx_cg *cg, double *rz);
  * preconditioner exclude each other: setting one replaces the other, and
  * cgx_cg_get_precond reports CGX_PRECOND_NONE while a block one is set.
  * Out of scope: block sizes that vary, bs > 8, f32, partitioned matrices, the
- * many-systems solver, the fused batch form, modes 4, 6 and 7. */
+ * fused batch form, modes 4, 6 and 7. (The many-systems solver has its own:
+ * cgx_many_set_block_precond.) */
 enum { CGX_BLOCK_NONE = 0, CGX_BLOCK_JACOBI = 1, CGX_BLOCK_GIVEN = 2 };
 /* d_out (n * bs values) = W for W_b the inverse of A's diagonal block b.
  * Row i of a block takes the entries of CSR row i whose column lies in the
@@ -578,12 +579,13 @@ int cgx_mixed_bytes(cgx_mixed *m, int64_t *bytes);
  * scaled 32 x 32 Poisson 3.85 against 1,998 for a cgx_cg_solve per system
  * (auto mode 5, create not counted) and 19.2 for one solve on the block-diagonal
  * assembly; irregular_spd(1000) 6.36 against 2,974 and 37.9.
- * Diagonal preconditioning (cgx_many_set_precond) runs in the same kernel: see
+ * Diagonal preconditioning (cgx_many_set_precond) and block-Jacobi
+ * preconditioning (cgx_many_set_block_precond) run in the same kernels: see
  * there.
- * Out of scope: f32 systems, a preconditioner other than a diagonal (the block
- * one above, cgx_cg_set_block_precond, is the single-system solver's), systems
- * with differing patterns, partitioned or multi-GPU use, and any auto route
- * from cgx_cg_solve into this path; in the wave form (cgx_many_set_form) also
+ * Out of scope: f32 systems, a preconditioner other than a diagonal or dense
+ * diagonal blocks of one size up to 8, systems with differing patterns,
+ * partitioned or multi-GPU use, and any auto route from cgx_cg_solve into
+ * this path; in the wave form (cgx_many_set_form) also
  * several systems per wave for n <= 32 and values cached in registers. */
 typedef struct cgx_many cgx_many;
 /* dtype: CGX_F64 (CGX_F32: CGX_EUNSUPPORTED). 1 <= n <= 4,096 (above:
@@ -694,6 +696,88 @@ int cgx_many_rz(cgx_many *m, double *rz_out);
 enum { CGX_MANY_FORM_AUTO = 0, CGX_MANY_FORM_WORKGROUP = 1, CGX_MANY_FORM_WAVE = 2 };
 int cgx_many_set_form(cgx_many *m, int form);
 int cgx_many_get_form(cgx_many *m, int *requested, int *in_effect);
+
+/* Block-Jacobi preconditioning inside the many-systems kernels, both forms:
+ * M^-1 = blockdiag(W_0, W_1, ...) per system, block b over rows [b bs,
+ * min((b + 1) bs, n)) with one bs in 1..8, as cgx_cg_set_block_precond's.
+ * System s's W is n x bs row-major at d_W + s * ldw, ldw >= n * bs, 8-byte
+ * aligned: W[i bs + j] = W_b[i - b bs, j]; the columns past a partial last
+ * block hold +0.0 and are never multiplied; [n bs, ldw) is never read, and
+ * cgx_many_block_inv never writes it. kind is CGX_BLOCK_NONE, CGX_BLOCK_JACOBI
+ * or CGX_BLOCK_GIVEN; it may be set between solves and takes effect at the
+ * next one (cgx_many_info then reports the block instantiation's grid, rows
+ * per thread and LDS: p, the staged r and the reduction words, the diagonal
+ * form's footprint). NONE ignores bs, d_W and ldw.
+ * JACOBI: d_W and ldw are ignored; the object owns an nsys x n bs workspace,
+ * allocated by this call (CGX_ENOMEM keeps what was set), and EVERY
+ * cgx_many_solve refills it from the values that solve reads, in a launch of
+ * its own before the CG kernel on the same stream: one thread per (system,
+ * block), cgx_csr_block_inv's statements (the lower triangle decides,
+ * duplicates summed from 0 in entry order, rows may be unsorted, LDL^T without
+ * pivoting, W mirrored). Values overwritten in place never meet a stale W.
+ * GIVEN: the caller's array, alive until replaced or cgx_many_destroy and read
+ * at every solve, as DIAGONAL's d_M; no copy is made. That each W_b is
+ * SYMMETRIC and POSITIVE DEFINITE is the caller's duty: CG with another M is
+ * not CG, and nothing here tests it.
+ * Arithmetic (normative): system s's x, body count, stop code, final r.r and
+ * final r.z equal, bit for bit, those of cgx_cg_solve in mode 1 with
+ * cgx_cg_set_block_precond(JACOBI, bs) (under GIVEN: (GIVEN, bs, W_s)) on that
+ * system alone, wherever the run's dots are clear of a rounding boundary:
+ * z_i = sum_j W[i bs + j] r_{b bs + j} from +0.0 in ascending j over the
+ * block's real columns, each product rounded before its add; p = z and
+ * rz = r.z at the start; per body alpha = rz / p.Ap, r -= alpha Ap, r.r and r.z
+ * double-length sums rounded once, beta = rz' / rz, x += alpha p,
+ * p = z + beta p; stop rule Q5 on the true r.r. With bs = 1 and JACOBI every
+ * value is the in-kernel Jacobi's on finite systems; with W the identity every
+ * value is the plain kernel's. A body has four barriers in the workgroup form
+ * (the staged r is published by the r.r sum's, r.z is a third sum) and none in
+ * the wave form; for n <= 64 the two forms give the same bits.
+ * A bad system stops alone: under JACOBI one with a pivot that is not positive
+ * and finite, a missing diagonal entry included; under GIVEN one with an entry
+ * of a real column that is not finite or a W_b[i, i] that is not positive and
+ * finite (checked at every solve in a launch before the CG kernel). Its X is
+ * left exactly as given and it reports 0 bodies, NaN r.r, NaN r.z and stop
+ * code 3; the call returns CGX_OK and no other system is touched.
+ * The diagonal and the block preconditioner exclude each other on a cgx_many:
+ * setting either replaces the other, NONE included; cgx_many_get_precond
+ * reports CGX_PRECOND_NONE while a block one is set; cgx_many_rz works under
+ * either. AUTO never chooses a block preconditioner.
+ * Measured with tools/many_block_pcg_bench.py on an MI355X (node_mixed
+ * principal systems scaled per system, to 1e-8 ||b||, three interleaved rounds
+ * after an untimed pass, medians; profiles/many_block_pcg_bench.log), µs per
+ * system in-kernel Jacobi -> block-Jacobi with the fill launch inside: 65,536
+ * systems of 60 rows, bs = 3 (wave form) 0.159 -> 0.058 (61 bodies, Jacobi's
+ * cap, -> 17); 4,096 of 396 rows, bs = 3, 9.04 -> 1.34 (313 -> 48); 4,096 of
+ * 392 rows, bs = 8, 40.5 -> 2.82 (375 -> 25); 4,096 of 3,000 rows, bs = 3,
+ * 186.4 -> 30.5 (814 -> 124). Every block round lay below every Jacobi and
+ * every plain round at each size. A block body costs 0.96 to 1.31 of a Jacobi
+ * body (1.31 in the wave form at 60 rows); the fill alone, timed as a
+ * blocking cgx_many_block_inv, is 1.5 to 10 % of the block solve.
+ * CGX_EINVAL, before any device call, for a NULL handle, an unknown kind, bs
+ * outside 1..8 (kind != NONE), GIVEN with a NULL or misaligned d_W or
+ * ldw < n * bs; on any error the object keeps what it had.
+ * cgx_many_get_block_precond: the block preconditioner in effect (*bs = 0
+ * with CGX_BLOCK_NONE); either output may be NULL.
+ * cgx_many_block_inv: the same fill into a caller's array (how a caller makes
+ * a GIVEN array); blocking. CGX_OK whether or not blocks are bad: *n_bad is
+ * the number of systems with a bad block, *first_bad the lowest such system
+ * or -1 (either may be NULL); a bad block's W holds whatever the statements
+ * give. CGX_EINVAL for a NULL handle, bs outside 1..8, a NULL or misaligned
+ * d_W, ldw < n * bs.
+ * cgx_many_block_bad: nsys host ints, 1 for each system the last
+ * cgx_many_block_inv found a bad block in (*n_bad of them, *first_bad the
+ * first); CGX_ESTATE before one has run, and after a solve since.
+ * Out of scope: block sizes that vary, bs > 8, f32, an auto route into block
+ * preconditioning, several systems per wave.
+ * Each of the four: Replaces nothing in the reference. */
+int cgx_many_set_block_precond(cgx_many *m, int kind, int bs, const void *d_W, int64_t ldw);
+/* Replaces nothing in the reference. */
+int cgx_many_get_block_precond(cgx_many *m, int *kind, int *bs);
+/* Replaces nothing in the reference. */
+int cgx_many_block_inv(cgx_many *m, int bs, void *d_W, int64_t ldw, int64_t *n_bad,
+                       int64_t *first_bad);
+/* Replaces nothing in the reference. */
+int cgx_many_block_bad(cgx_many *m, int *bad_out);
 
 /* CG::accuracy (CG.hpp:463-515): blocking; |sum (b-Ax)^2 / sum x^2|. */
 int cgx_accuracy(cgx_ctx *ctx, cgx_csr *A, const void *d_b, const void *d_x,
