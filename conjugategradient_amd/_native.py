@@ -124,6 +124,9 @@ _SIGS = {
     "cgx_cg_run_batch": (_i32, [_vp, _i64, C.POINTER(_i64), C.POINTER(_i32)]),
     "cgx_cg_set_batch_form": (_i32, [_vp, _i32]),
     "cgx_cg_batch_info": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "cgx_cg_solve_shifted": (_i32, [_vp, _i32, C.POINTER(_dbl), _vp, _vp, _i64, _dbl, _i64,
+                                    C.POINTER(_i64), C.POINTER(_dbl), C.POINTER(_i32)]),
+    "cgx_cg_shifted_zeta": (_i32, [_vp, C.POINTER(_dbl)]),
     "cgx_mixed_create": (_i32, [_vp, _vp, C.POINTER(_vp)]),
     "cgx_mixed_destroy": (_i32, [_vp]),
     "cgx_mixed_config": (_i32, [_vp, _dbl, _i32, _i64]),

@@ -412,6 +412,9 @@ class CG:
         self.iterations_batch = None  # extension (solve_batch): loop bodies per column
         self.final_rxr_batch = None   # r.r after each column's last body
         self.stopped_batch = None     # 1 stop rule / NaN, 2 cap reached, per column
+        self.iterations_shifted = None  # extension (solve_shifted): loop bodies per shift
+        self.residual_shifted = None    # |zeta_s| ||r|| after each shift's last body
+        self.stopped_shifted = None     # 1 frozen by the rule, 2 cap reached, per shift
         self._mixed = None        # cgx_mixed handle (solve_mixed), built on first use
         self._mixed_for = None
         self._mixed_cfg = None    # the (mode, preconditioner) its inner solver was given
@@ -732,6 +735,41 @@ class CG:
         form, width = C.c_int(0), C.c_int(0)
         check(lib().cgx_cg_batch_info(cg, C.byref(form), C.byref(width)))
         return form.value, width.value
+
+    MAX_SHIFTS = 8  # cgx.h CGX_SHIFT_MAX
+
+    def solve_shifted(self, sigmas, improvement: float = 0.0, max_iter: int = -1) -> np.ndarray:
+        """Extension (cgx_cg_solve_shifted): (A + sigma_s I) x_s = b for
+        S = 1..8 shifts sigma_s >= 0 on ``setTarget``'s b, every x_s from zero,
+        all from one Krylov space (one SpMV and one pair of dots per body).
+        Returns X (n, S) and sets ``iterations_shifted``, ``residual_shifted``
+        (|zeta_s| ||r|| after each shift's last body) and ``stopped_shifted``
+        (1 frozen by the rule, 2 cap reached). A sigma = 0 column is the single
+        mode-1 solve from a zero initial guess, bit for bit. ValueError, before
+        any device call, for S outside 1..8 or a shift that is negative or not
+        finite."""
+        sg = np.atleast_1d(np.asarray(sigmas, dtype=np.float64))
+        if sg.ndim != 1 or not 1 <= sg.size <= self.MAX_SHIFTS:
+            raise ValueError(f"a shifted solve has 1 to {self.MAX_SHIFTS} shifts, got "
+                             f"{sg.size if sg.ndim == 1 else sg.shape}")
+        if not np.all(np.isfinite(sg)) or np.any(sg < 0):
+            raise ValueError(f"a shift is finite and not negative, got {sg.tolist()}")
+        if self.b.ptr() is None:
+            raise RuntimeError("No right hand side to solve for")
+        if self.A.columns() is None:
+            raise RuntimeError("No Matrix given")
+        n, k = self.A.N(), int(sg.size)
+        dX = DeviceArray(self._queue, n * k, self.dtype)
+        bodies = (C.c_int64 * k)()
+        res = (C.c_double * k)()
+        stopped = (C.c_int * k)()
+        check(lib().cgx_cg_solve_shifted(self._solver(), k, (C.c_double * k)(*sg.tolist()),
+                                         self.b.ptr(), dX.ptr, n, float(improvement),
+                                         int(max_iter), bodies, res, stopped))
+        self.iterations_shifted = np.array(bodies[:], dtype=np.int64)
+        self.residual_shifted = np.array(res[:], dtype=np.float64)
+        self.stopped_shifted = np.array(stopped[:], dtype=np.int32)
+        return np.ascontiguousarray(dX.download().reshape(k, n).T)
 
     # -- outputs --------------------------------------------------------
     def accuracy(self) -> float:

@@ -3561,6 +3561,7 @@ extern "C" int cgx_cg_set_precond(cgx_cg *cg, int kind, const void *d_minv) {
   CGX_HIP(hipStreamSynchronize(s));
   drop_graph(cg, cg->graphs);
   drop_graph(cg, cg->bt.graphs);
+  drop_graph(cg, cg->sh.graphs);
   cg->begun = false;
   cg->bt.begun = false;
   if (cg->minv_own) (void)hipFree(cg->minv_own);
@@ -3675,6 +3676,7 @@ extern "C" int cgx_cg_set_block_precond(cgx_cg *cg, int kind, int bs, const void
   CGX_HIP(hipStreamSynchronize(cg->ctx->stream));
   drop_graph(cg, cg->graphs);
   drop_graph(cg, cg->bt.graphs);
+  drop_graph(cg, cg->sh.graphs);
   cg->begun = false;
   cg->bt.begun = false;
   if (cg->blk_w) (void)hipFree(cg->blk_w);
@@ -3733,14 +3735,17 @@ extern "C" int cgx_cg_destroy(cgx_cg *cg) {
   (void)hipStreamSynchronize(cg->ctx->stream);
   drop_graph(cg, cg->graphs);
   drop_graph(cg, cg->bt.graphs);
+  drop_graph(cg, cg->sh.graphs);
   for (auto e : cg->ev_pool) (void)hipEventDestroy(e);
   for (hipEvent_t e : cg->run_ev)
     if (e) (void)hipEventDestroy(e);
   for (void *p : {cg->r, cg->p, cg->p2, cg->Ap, cg->st, cg->ws, cg->pk[0], cg->pk[1], cg->pk[2],
                   cg->coop_ws, cg->coop_trace, cg->minv_own, cg->blk_w, cg->bt.r, cg->bt.p,
-                  cg->bt.Ap, cg->bt.st, cg->bt.ws, cg->bt.seq_b, cg->bt.seq_x})
+                  cg->bt.Ap, cg->bt.st, cg->bt.ws, cg->bt.seq_b, cg->bt.seq_x, cg->sh.ps,
+                  cg->sh.state})
     if (p) (void)hipFree(p);
   if (cg->bt.h_poll) (void)hipHostFree(cg->bt.h_poll);
+  if (cg->sh.h_poll) (void)hipHostFree(cg->sh.h_poll);
   cgx_csr *A = cg->A;
   cgx_ctx *ctx = cg->ctx;
   delete cg;
@@ -3755,6 +3760,7 @@ extern "C" int cgx_cg_config(cgx_cg *cg, int poll_every, int use_graph) {
     if (poll_every != cg->poll_every) {
       drop_graph(cg, cg->graphs);
       drop_graph(cg, cg->bt.graphs);
+      drop_graph(cg, cg->sh.graphs);
     }
     cg->poll_every = poll_every;
   }
@@ -4261,6 +4267,171 @@ extern "C" int cgx_cg_solve_batch(cgx_cg *cg, int nrhs, const void *d_B, int64_t
     rxr_out[c] = rxr;
     if (stopped_out) stopped_out[c] = stopped;
   }
+  return CGX_OK;
+}
+
+// ===========================================================================
+// multi-shift CG: one matrix under several diagonal shifts
+// ===========================================================================
+namespace {
+// one poll: the base ring, then the shifts' state
+constexpr size_t kShiftPollBytes = sizeof(CgScalars<double>) + sizeof(ShiftState);
+
+const char *shifted_refusal(const cgx_cg *cg) {
+  if (cg->dtype != CGX_F64) return "the solver is f32 (multi-shift CG is f64)";
+  if (cg->A->dist) return "the matrix is partitioned (cgx_csr_create_dist)";
+  if (has_precond(cg))
+    return "a preconditioner is set (M (A + sigma I) is not a shift of M A)";
+  return nullptr;
+}
+
+int shifted_alloc(cgx_cg *cg, int nshift) {
+  auto &h = cg->sh;
+  hipStream_t s = cg->ctx->stream;
+  if (h.cap_shifts < nshift) {
+    CGX_HIP(hipStreamSynchronize(s));
+    drop_graph(cg, h.graphs);
+    if (h.ps) CGX_HIP(hipFree(h.ps));
+    h.ps = nullptr;
+    h.cap_shifts = 0;
+    // n + 2 doubles per shift, an even count: every p_s is 16-byte aligned
+    h.stride = ((int64_t)cg->n + 3) & ~(int64_t)1;
+    const size_t bytes = (size_t)h.stride * (size_t)nshift * sizeof(double);
+    CGX_HIP(hipMalloc(&h.ps, bytes));
+    CGX_HIP(hipMemsetAsync(h.ps, 0, bytes, s));
+    h.cap_shifts = nshift;
+  }
+  if (!h.state) {
+    CGX_HIP(hipMalloc(&h.state, sizeof(ShiftState)));
+    CGX_HIP(hipMemsetAsync(h.state, 0, sizeof(ShiftState), s));
+  }
+  if (!h.h_poll) CGX_HIP(hipHostMalloc(&h.h_poll, 2 * kShiftPollBytes));
+  return CGX_OK;
+}
+
+// The mode-1 body shape with the shifted update as its third launch; sweep
+// directions as a three-launch body's (cgx_sweep.h)
+int enqueue_iter_shifted(cgx_cg *cg, int slot) {
+  auto &h = cg->sh;
+  hipStream_t s = cg->ctx->stream;
+  const CsrDev &A = cg->A->dev;
+  const CgView<double> v(cg);
+  const int d0 = cg->altdir ? sweep_dir(3, slot & 3, 0) : 0;
+  const int d1 = cg->altdir ? sweep_dir(3, slot & 3, 1) : 0;
+  const int d2 = cg->altdir ? sweep_dir(3, slot & 3, 2) : 0;
+  CGX_HIP(Launch<double>::spmv_dot(A, v.P[0], v.Ap, v.st, slot, v.ws, s, d0));
+  CGX_HIP(Launch<double>::update_r(cg->n, v.r, v.Ap, v.st, slot, v.ws, s, false,
+                                   Launch<double>::spmv_parts(A), d1));
+  CGX_HIP(shift_update_xp(cg->n, h.nshift, v.P[0], v.r, v.st, (ShiftState *)h.state, slot, v.ws,
+                          Launch<double>::update_parts(cg->n), d2, h.ptrs, s));
+  return CGX_OK;
+}
+
+int shifted_poll(cgx_cg *cg, char *hdst, hipStream_t s) {
+  CGX_HIP(hipMemcpyAsync(hdst, cg->st, sizeof(CgScalars<double>), hipMemcpyDeviceToHost, s));
+  CGX_HIP(hipMemcpyAsync(hdst + sizeof(CgScalars<double>), cg->sh.state, sizeof(ShiftState),
+                         hipMemcpyDeviceToHost, s));
+  return CGX_OK;
+}
+}  // namespace
+
+extern "C" int cgx_cg_solve_shifted(cgx_cg *cg, int nshift, const double *h_sigma, const void *d_b,
+                                    void *d_X, int64_t ldx, double tol, int64_t max_bodies,
+                                    int64_t *bodies_out, double *res_out, int *stopped_out) {
+  CGX_REQUIRE(cg, CGX_EINVAL, "cg is NULL");
+  CGX_REQUIRE(nshift >= 1 && nshift <= CGX_SHIFT_MAX, CGX_EINVAL,
+              "nshift = %d: a shifted solve has 1 to %d shifts", nshift, (int)CGX_SHIFT_MAX);
+  CGX_REQUIRE(h_sigma && d_b && d_X && bodies_out && res_out, CGX_EINVAL,
+              "h_sigma, d_b, d_X, bodies_out or res_out is NULL");
+  CGX_REQUIRE(ldx >= cg->n, CGX_EINVAL, "ldx = %lld: a leading dimension is at least n = %lld",
+              (long long)ldx, (long long)cg->n);
+  for (int k = 0; k < nshift; ++k)
+    CGX_REQUIRE(std::isfinite(h_sigma[k]) && h_sigma[k] >= 0.0, CGX_EINVAL,
+                "shift %d is %g: a shift is finite and not negative (A + sigma I stays SPD)", k,
+                h_sigma[k]);
+  if (const char *why = shifted_refusal(cg)) {
+    set_error("cgx_cg_solve_shifted: %s", why);
+    return CGX_EUNSUPPORTED;
+  }
+  CGX_REQUIRE(((uintptr_t)d_X & 7) == 0 && ((uintptr_t)d_b & 7) == 0, CGX_EINVAL,
+              "d_b and d_X must be 8-byte aligned");
+  DeviceGuard g(cg->ctx->device);
+  hipStream_t s = cg->ctx->stream;
+  auto &h = cg->sh;
+  const long long cap = body_cap(cg->n, max_bodies);
+  cg->begun = false;     // a single solve in progress ends here
+  cg->bt.begun = false;  // and a batch
+  if (int rc = shifted_alloc(cg, nshift)) return rc;
+  if (h.graph_s != nshift || h.graph_x != d_X || h.graph_ldx != ldx) drop_graph(cg, h.graphs);
+  h.graph_s = nshift;
+  h.graph_x = d_X;
+  h.graph_ldx = ldx;
+  h.nshift = nshift;
+  h.ptrs = ShiftPtrs{};
+  for (int k = 0; k < nshift; ++k) {
+    h.ptrs.x[k] = (double *)d_X + (size_t)k * (size_t)ldx;
+    h.ptrs.p[k] = (double *)h.ps + (size_t)k * (size_t)h.stride;
+  }
+  const CgView<double> v(cg);
+  auto *state = (ShiftState *)h.state;
+  if (cg->n > 0) {
+    // x_s = 0 and p_s = b, then the single solve's init against the zeroed
+    // column 0: the base ring and rxr[0] are cgx_cg_begin's from x = 0. A
+    // column 0 that is not 16-byte aligned cannot serve (the init SpMV reads
+    // pairs): the zeroed Ap buffer then
+    CGX_HIP(shift_init(cg->n, nshift, h_sigma, (const double *)d_b, h.ptrs, state, s));
+    const double *zero = h.ptrs.x[0];
+    if ((uintptr_t)zero & 15) {
+      CGX_HIP(hipMemsetAsync(cg->Ap, 0, (size_t)cg->n * sizeof(double), s));
+      zero = v.Ap;
+    }
+    CGX_HIP(Launch<double>::cg_init(cg->A->dev, zero, (const double *)d_b, v.r, v.P[0], v.st, v.ws,
+                                    tol, cap, s));
+  }
+  h.slot = 0;
+  auto *hbuf = (char *)h.h_poll;
+  int last_buf = -1;
+  int rc = run_chunks(
+      cg, &h.slot, cg->n > 0 ? (int64_t)cap : 0,
+      [&](int64_t remaining) { return std::min<int64_t>(remaining, cg->poll_every); },
+      [&](int slot0, int64_t chunk) {
+        return enqueue_chunk(cg, cg->use_graph ? &h.graphs : nullptr, slot0, chunk,
+                             [&](int slot) { return enqueue_iter_shifted(cg, slot); });
+      },
+      [&](int buf) { return shifted_poll(cg, hbuf + kShiftPollBytes * buf, s); },
+      [&](int buf, int slot_after) {
+        last_buf = buf;
+        return ((const CgScalars<double> *)(hbuf + kShiftPollBytes * buf))->active[slot_after] != 0;
+      },
+      [] { return CGX_OK; });
+  if (rc) return rc;
+  CGX_HIP(hipStreamSynchronize(s));
+  if (last_buf < 0) {  // a matrix without rows: nothing ran
+    for (int k = 0; k < nshift; ++k) {
+      bodies_out[k] = 0;
+      res_out[k] = 0.0;
+      if (stopped_out) stopped_out[k] = 1;
+    }
+    h.nshift = 0;
+    return CGX_OK;
+  }
+  // the last poll to the front: cgx_cg_shifted_zeta reads it there
+  if (last_buf != 0) std::memcpy(hbuf, hbuf + kShiftPollBytes * last_buf, kShiftPollBytes);
+  const auto *st = (const ShiftState *)(hbuf + sizeof(CgScalars<double>));
+  for (int k = 0; k < nshift; ++k) {
+    bodies_out[k] = st->bodies[k];
+    res_out[k] = std::fabs(st->zeta[st->bodies[k] & 3][k]) * std::sqrt(st->rr[k]);
+    if (stopped_out) stopped_out[k] = st->code[k];
+  }
+  return CGX_OK;
+}
+
+extern "C" int cgx_cg_shifted_zeta(cgx_cg *cg, double *zeta_out) {
+  CGX_REQUIRE(cg && zeta_out, CGX_EINVAL, "NULL argument");
+  CGX_REQUIRE(cg->sh.nshift > 0 && cg->sh.h_poll, CGX_ESTATE,
+              "cgx_cg_shifted_zeta before cgx_cg_solve_shifted");
+  const auto *st = (const ShiftState *)((const char *)cg->sh.h_poll + sizeof(CgScalars<double>));
+  for (int k = 0; k < cg->sh.nshift; ++k) zeta_out[k] = st->zeta[st->bodies[k] & 3][k];
   return CGX_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "cgx_shift.h"
 #include "cgx_variant.h"
 
 namespace cgx {
@@ -161,6 +162,37 @@ struct BatchWs {
   double pap[kBatchMax][2 * kMaxGrid];
   double rr[kBatchMax][2 * kMaxGrid];
 };
+
+// ---- multi-shift CG (cgx_cg_solve_shifted; cgx_kernels.hip) ------
+// The shifts' device state. The rings are indexed like CgScalars': the body
+// in slot s reads zeta[s] (zeta_n), zeta[s - 1] (zeta_{n-1}), ap[s], bp[s]
+// (alpha_{n-1}, beta_{n-1}) and mask[s] (bit k: shift k runs this body), and
+// its last launch writes slot s + 1 of each, which no workgroup of the body
+// reads. A frozen shift's entries are not written again: its last zeta sits
+// at zeta[bodies & 3].
+struct ShiftState {
+  double sigma[kShiftMax];
+  double zeta[4][kShiftMax];
+  double ap[4], bp[4];
+  double rr[kShiftMax];         // the base r.r after the shift's last body
+  long long bodies[kShiftMax];  // bodies the shift ran
+  int code[kShiftMax];          // 0 running, 1 frozen by the rule, 2 cap reached
+  int mask[4];
+  int nshift, pad;
+};
+// kernel argument (by value): shift k's column of X and its direction vector
+struct ShiftPtrs {
+  double *x[kShiftMax];
+  double *p[kShiftMax];
+};
+// x_s = 0, p_s = b, zeta = 1, every shift active in slot 0 (h_sigma: host);
+// Launch<double>::cg_init on a zeroed column follows it
+hipError_t shift_init(int64_t n, int nshift, const double *h_sigma, const double *b,
+                      const ShiftPtrs &P, ShiftState *sh, hipStream_t s);
+// the body's third launch, in update_xp's place (np_rr: update_r's partials)
+hipError_t shift_update_xp(int64_t n, int nshift, double *p, const double *r,
+                           CgScalars<double> *st, ShiftState *sh, int slot, RedWs<double> *ws,
+                           int np_rr, int rev, const ShiftPtrs &P, hipStream_t s);
 
 struct SellSlice {
   int64_t voff;  // first value of the slice (entries)

@@ -7974,6 +7974,293 @@ hipError_t il_build(const CsrDev &A, int es, char *il, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Multi-shift CG (cgx_cg_solve_shifted): up to kShiftMax
+// systems (A + sigma_s I) x_s = b from one Krylov space. The body is the
+// mode-1 shape: k_spmv_dot and k_update_r of the base recurrence on A,
+// unchanged, then k_update_xp_shift in k_update_xp's place: the base p update
+// and every active shift's x_s and p_s update. The shifted residuals stay
+// collinear with the base one (r_s = zeta_s r), so a shift adds no SpMV and
+// no dot, only its own 32 N bytes per body. The per-element expressions are
+// k_update_xp's, and a sigma = 0 shift is the single mode-1 solve bit for bit
+// (cgx_shift.h).
+// ---------------------------------------------------------------------------
+namespace shiftk {
+typedef double D2 __attribute__((ext_vector_type(2)));
+
+
+template <bool NT> __device__ __forceinline__ D2 ld2(const double *q) {
+  if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const D2 *>(q));
+  else return *reinterpret_cast<const D2 *>(q);
+}
+template <bool NT> __device__ __forceinline__ void st2(double *q, D2 v) {
+  if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<D2 *>(q));
+  else *reinterpret_cast<D2 *>(q) = v;
+}
+// rows 2 j, 2 j + 1 of a column of X: one 16-byte access when the column is
+// 16-byte aligned (al, uniform per column), else two of 8 bytes
+template <bool NT> __device__ __forceinline__ D2 ldx2(const double *q, bool al) {
+  if (al) return ld2<NT>(q);
+  D2 v;
+  if constexpr (NT) {
+    v.x = __builtin_nontemporal_load(q);
+    v.y = __builtin_nontemporal_load(q + 1);
+  } else {
+    v.x = q[0];
+    v.y = q[1];
+  }
+  return v;
+}
+template <bool NT> __device__ __forceinline__ void stx2(double *q, D2 v, bool al) {
+  if (al) {
+    st2<NT>(q, v);
+  } else if constexpr (NT) {
+    __builtin_nontemporal_store(v.x, q);
+    __builtin_nontemporal_store(v.y, q + 1);
+  } else {
+    q[0] = v.x;
+    q[1] = v.y;
+  }
+}
+
+// a workgroup-uniform double into scalar registers
+__device__ __forceinline__ double uni(double v) {
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
+
+// U pairs of rows per thread and trip: every load of the trip is issued
+// before the arithmetic (at most 2 + 2 SM 16-byte loads per pair of rows)
+template <bool NT, int SM> struct ShiftRows {
+  double *p;
+  const double *r;
+  ShiftPtrs P;
+  unsigned am, al;  // active shifts; columns of X that are 16-byte aligned
+  double bt;
+  double zn[SM], as[SM], bs[SM];
+  int64_t n2, stride;
+  int rev;
+
+  template <int U> __device__ __forceinline__ void go(int64_t i) const {
+    D2 rv[U], pv[U], xs[U][SM], ps[U][SM];
+    int64_t e[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t j = i + u * stride;
+      e[u] = 2 * (rev ? n2 - 1 - j : j);  // sweep direction
+      rv[u] = ld2<NT>(r + e[u]);          // r is read here for the last time
+      pv[u] = ld2<false>(p + e[u]);
+#pragma unroll
+      for (int s = 0; s < SM; ++s) {
+        if ((am >> s) & 1u) {
+          xs[u][s] = ldx2<NT>(P.x[s] + e[u], (al >> s) & 1u);
+          ps[u][s] = ld2<NT>(P.p[s] + e[u]);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int s = 0; s < SM; ++s) {
+        if ((am >> s) & 1u) {
+          D2 xv = xs[u][s], qv = ps[u][s];
+          xv.x = xv.x + as[s] * qv.x;
+          xv.y = xv.y + as[s] * qv.y;
+          qv.x = zn[s] * rv[u].x + bs[s] * qv.x;
+          qv.y = zn[s] * rv[u].y + bs[s] * qv.y;
+          stx2<NT>(P.x[s] + e[u], xv, (al >> s) & 1u);
+          st2<NT>(P.p[s] + e[u], qv);
+        }
+      }
+      D2 pn;
+      pn.x = rv[u].x + bt * pv[u].x;
+      pn.y = rv[u].y + bt * pv[u].y;
+      st2<false>(p + e[u], pn);  // the SpMV reads it next
+    }
+  }
+};
+
+// Third launch of a multi-shift body in `slot`: beta from k_update_r's r.r
+// partials as k_update_xp forms it; shift_step for each active shift (thread s
+// of every workgroup takes shift s; the results go through LDS into scalar
+// registers); x_s += as p_s, p_s = zn r + bs p_s for the active shifts and
+// p = r + beta p; workgroup 0's thread 0 writes the base ring as k_update_xp
+// does and each active shift's zeta, body count, code and r.r. The base goes
+// on while any shift is active. ShiftState's rings are indexed like
+// CgScalars': this launch reads slots `slot` and `slot - 1` and writes
+// `slot + 1`.
+template <bool NT, int SM, int U>
+__global__ __launch_bounds__(kBlock) void k_update_xp_shift(int64_t n, double *p, const double *r,
+                                                            CgScalars<double> *st, ShiftState *sh,
+                                                            int slot, RedWs<double> *ws, int np_rr,
+                                                            int rev, ShiftPtrs P, unsigned al) {
+  const int nxt = (slot + 1) & 3, prv = (slot + 3) & 3;
+  const bool rec = blockIdx.x == 0 && threadIdx.x == 0;
+  if (!st->active[slot]) {
+    if (rec) {
+      st->active[nxt] = 0;
+      sh->mask[nxt] = 0;
+    }
+    return;
+  }
+  __shared__ double red[8];
+  __shared__ double sc[3 * kShiftMax];
+  __shared__ int sstop[kShiftMax];
+  const double rxr = st->rxr[slot];
+  const double a = rxr / st->pAp[slot];
+  const double rr = sum_parts_dd(ws->rr_part, np_rr, red).value();
+  const double bt = rr / rxr;
+  const unsigned am = (unsigned)sh->mask[slot];
+  if (threadIdx.x < SM && ((am >> threadIdx.x) & 1u)) {
+    const int s = threadIdx.x;
+    const ShiftStep o = shift_step(a, bt, sh->ap[slot], sh->bp[slot], sh->sigma[s],
+                                   sh->zeta[slot][s], sh->zeta[prv][s], rxr, st->tol);
+    sc[3 * s] = o.zn;
+    sc[3 * s + 1] = o.as;
+    sc[3 * s + 2] = o.bs;
+    sstop[s] = o.stop ? 1 : 0;
+  }
+  __syncthreads();
+  ShiftRows<NT, SM> w;
+  w.p = p;
+  w.r = r;
+  w.P = P;
+  w.am = am;
+  w.al = al;
+  w.bt = bt;
+#pragma unroll
+  for (int s = 0; s < SM; ++s) {
+    const bool on = (am >> s) & 1u;
+    w.zn[s] = on ? uni(sc[3 * s]) : 0.0;
+    w.as[s] = on ? uni(sc[3 * s + 1]) : 0.0;
+    w.bs[s] = on ? uni(sc[3 * s + 2]) : 0.0;
+  }
+  w.n2 = n >> 1;
+  w.stride = (int64_t)gridDim.x * kBlock;
+  w.rev = rev;
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if constexpr (U > 1) {
+    for (; i + (U - 1) * w.stride < w.n2; i += U * w.stride) w.template go<U>(i);
+  }
+  for (; i < w.n2; i += w.stride) w.template go<1>(i);
+  if (rec) {
+    if (n & 1) {  // the last row of an odd n
+      const double rv = r[n - 1];
+#pragma unroll
+      for (int s = 0; s < SM; ++s) {
+        if ((am >> s) & 1u) {
+          const double qv = P.p[s][n - 1];
+          P.x[s][n - 1] = P.x[s][n - 1] + w.as[s] * qv;
+          P.p[s][n - 1] = w.zn[s] * rv + w.bs[s] * qv;
+        }
+      }
+      p[n - 1] = rv + bt * p[n - 1];
+    }
+    st->rr[slot] = rr;  // the base ring, as k_update_xp
+    const long long m = st->bodies + 1;
+    st->bodies = m;
+    const bool capped = m >= st->cap;
+    unsigned nm = 0;
+    bool any2 = false;
+#pragma unroll
+    for (int s = 0; s < SM; ++s) {
+      if ((am >> s) & 1u) {
+        const bool stop = sstop[s] != 0;
+        sh->zeta[nxt][s] = w.zn[s];
+        sh->bodies[s] = m;
+        sh->rr[s] = rr;
+        sh->code[s] = stop ? 1 : (capped ? 2 : 0);
+        if (!stop && !capped) nm |= 1u << s;
+        if (!stop && capped) any2 = true;
+      }
+    }
+    sh->mask[nxt] = (int)nm;
+    sh->ap[nxt] = a;
+    sh->bp[nxt] = bt;
+    st->active[nxt] = nm ? 1 : 0;
+    st->rxr[nxt] = rr;
+    st->stopped = nm ? 0 : (any2 ? 2 : 1);
+  }
+}
+
+struct ShiftSigma {
+  double v[kShiftMax];
+};
+
+// after this, Launch::cg_init on column 0 of X: x_s = 0, p_s = b, zeta = 1
+__global__ __launch_bounds__(kBlock) void k_shift_init(int64_t n, int nshift,
+                                                       const double *__restrict__ b, ShiftPtrs P,
+                                                       ShiftSigma sg, ShiftState *sh) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    const double bv = b[i];
+    for (int s = 0; s < nshift; ++s) {
+      P.x[s][i] = 0.0;
+      P.p[s][i] = bv;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    for (int s = 0; s < kShiftMax; ++s) {
+      sh->sigma[s] = s < nshift ? sg.v[s] : 0.0;
+      for (int t = 0; t < 4; ++t) sh->zeta[t][s] = 1.0;
+      sh->rr[s] = 0.0;
+      sh->bodies[s] = 0;
+      sh->code[s] = 0;
+    }
+    for (int t = 0; t < 4; ++t) {
+      sh->ap[t] = 1.0;
+      sh->bp[t] = 0.0;
+      sh->mask[t] = 0;
+    }
+    sh->mask[0] = (1 << nshift) - 1;
+    sh->nshift = nshift;
+    sh->pad = 0;
+  }
+}
+}  // namespace shiftk
+
+hipError_t shift_init(int64_t n, int nshift, const double *h_sigma, const double *b,
+                      const ShiftPtrs &P, ShiftState *sh, hipStream_t s) {
+  if (nshift < 1 || nshift > kShiftMax) return hipErrorInvalidValue;
+  shiftk::ShiftSigma sg{};
+  for (int k = 0; k < nshift; ++k) sg.v[k] = h_sigma[k];
+  hipLaunchKernelGGL(shiftk::k_shift_init, dim3(Launch<double>::grid_elems(n, kGridUpdateP)), dim3(kBlock), 0, s, n,
+                     nshift, b, P, sg, sh);
+  return hipGetLastError();
+}
+
+hipError_t shift_update_xp(int64_t n, int nshift, double *p, const double *r,
+                           CgScalars<double> *st, ShiftState *sh, int slot, RedWs<double> *ws,
+                           int np_rr, int rev, const ShiftPtrs &P, hipStream_t s) {
+  if (nshift < 1 || nshift > kShiftMax || np_rr < 1) return hipErrorInvalidValue;
+  unsigned al = 0;
+  for (int k = 0; k < nshift; ++k) {
+    if (((uintptr_t)P.p[k] & 15) != 0) return hipErrorInvalidValue;
+    if (((uintptr_t)P.x[k] & 15) == 0) al |= 1u << k;
+  }
+  const bool nt = kStreamNt && n * (int64_t)sizeof(double) > kNtVecBytes;  // stream_nt
+  const dim3 g(Launch<double>::grid_elems(n, kGridUpdateP)), blk(kBlock);
+#define CGX_SHIFT_GO(NT, SM, U)                                                                  \
+  hipLaunchKernelGGL((shiftk::k_update_xp_shift<NT, SM, U>), g, blk, 0, s, n, p, r, st, sh, slot, ws,    \
+                     np_rr, rev, P, al)
+  // loads in flight per thread and trip: 4 (2 + 2 S) for up to 2 shifts,
+  // 2 (2 + 2 S) for up to 4, 2 + 2 S beyond
+  if (nshift <= 2) {
+    if (nt) CGX_SHIFT_GO(true, 2, 4);
+    else CGX_SHIFT_GO(false, 2, 4);
+  } else if (nshift <= 4) {
+    if (nt) CGX_SHIFT_GO(true, 4, 2);
+    else CGX_SHIFT_GO(false, 4, 2);
+  } else {
+    if (nt) CGX_SHIFT_GO(true, 8, 1);
+    else CGX_SHIFT_GO(false, 8, 1);
+  }
+#undef CGX_SHIFT_GO
+  return hipGetLastError();
+}
+
 template struct Launch<double>;
 template struct Launch<float>;
 

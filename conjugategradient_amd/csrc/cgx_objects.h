@@ -310,6 +310,25 @@ struct cgx_cg {
     int64_t graph_ldx = 0;
     int graph_w = 0;
   } bt;
+  // multi-shift CG (cgx_cg_solve_shifted). The base r, p and Ap
+  // are the solver's own; the shifts' direction vectors and state are
+  // allocated on first use and freed with the solver.
+  struct Shifted {
+    int nshift = 0;           // shifts of the last solve (0: none yet)
+    int cap_shifts = 0;       // direction vectors allocated
+    void *ps = nullptr;       // cap_shifts vectors of `stride` doubles (>= n + 2, even)
+    int64_t stride = 0;
+    void *state = nullptr;    // cgx::ShiftState
+    void *h_poll = nullptr;   // pinned: two copies of {CgScalars<double>, ShiftState}
+    cgx::ShiftPtrs ptrs{};
+    int slot = 0;
+    // captured chunks, for nshift = graph_s and X = graph_x at leading
+    // dimension graph_ldx
+    cgx::GraphCache graphs;
+    void *graph_x = nullptr;
+    int64_t graph_ldx = 0;
+    int graph_s = 0;
+  } sh;
   // kernel timing
   bool timing = false;
   std::vector<hipEvent_t> ev_pool;

@@ -328,6 +328,55 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
   const std::vector<double> &batchFinalResidualSquared() const { return _batch_rxr; }
   const std::vector<int> &batchStopped() const { return _batch_stopped; }
 
+  /**
+   * Multi-shift solve (cgx_cg_solve_shifted of cgx.h): (A + sigma[s] I) x_s = b
+   * for 1 to 8 shifts sigma[s] >= 0 on the matrix and the right-hand side
+   * (setTarget) in place, every x_s from zero, all from one Krylov space. X is
+   * resized to sigma.size() vectors of N and receives the solutions (copied
+   * from column-major device storage). A sigma = 0 column is the single solve
+   * in mode 1 from a zero initial guess, bit for bit. f64 without a
+   * preconditioner (else the cgx error is thrown).
+   * @throw std::invalid_argument for a shift count outside 1..8 or a shift
+   *        that is negative or not finite
+   */
+  void solveShifted(const std::vector<DT> &sigma, std::vector<Vector> &X,
+                    DT improvement = static_cast<DT>(0)) {
+    const std::size_t k = sigma.size(), n = static_cast<std::size_t>(A.N());
+    if (k < 1 || k > 8) throw std::invalid_argument("solveShifted: 1 to 8 shifts");
+    std::vector<double> sg(k);
+    for (std::size_t c = 0; c < k; ++c) {
+      sg[c] = static_cast<double>(sigma[c]);
+      if (!(sg[c] >= 0.0) || sg[c] > std::numeric_limits<double>::max())
+        throw std::invalid_argument("solveShifted: a shift is finite and not negative");
+    }
+    if (this->b.data() == nullptr) throw std::runtime_error("No right hand side to solve for");
+    if (this->A.columns().get() == nullptr) throw std::runtime_error("No Matrix given");
+    Vector Xd(_queue, n * k);
+    cgx_cg *s = solver();
+    std::vector<int64_t> bodies(k);
+    std::vector<double> res(k);
+    std::vector<int> stopped(k);
+    check(cgx_cg_solve_shifted(s, static_cast<int>(k), sg.data(), b.ptr(), Xd.ptr(),
+                               static_cast<int64_t>(n), (double)improvement, _max_iterations,
+                               bodies.data(), res.data(), stopped.data()),
+          "solveShifted");
+    X.clear();
+    for (std::size_t c = 0; c < k; ++c) {
+      X.emplace_back(_queue);
+      X[c].init_empty(n);
+      check(cgx_d2d(_queue.native(), X[c].ptr(), Xd.ptr() + c * n, n * sizeof(DT)), "solveShifted");
+    }
+    check(cgx_sync(_queue.native()), "solveShifted");
+    _shifted_iterations.assign(bodies.begin(), bodies.end());
+    _shifted_res = res;
+    _shifted_stopped = stopped;
+  }
+  /** per shift of the last solveShifted: loop bodies, |zeta_s| ||r|| after the
+   * shift's last body, stop code (1 frozen by the rule, 2 cap reached) */
+  const std::vector<long long> &shiftedIterations() const { return _shifted_iterations; }
+  const std::vector<double> &shiftedResidual() const { return _shifted_res; }
+  const std::vector<int> &shiftedStopped() const { return _shifted_stopped; }
+
   /** one residual evaluation of solveMixed (cgx_mixed_history) */
   struct MixedRecord {
     double rr;               ///< the f64 true r.r
@@ -502,6 +551,9 @@ template <typename DT, Debuglevel debug = Debuglevel::None> class CG {
   std::vector<long long> _batch_iterations;
   std::vector<double> _batch_rxr;
   std::vector<int> _batch_stopped;
+  std::vector<long long> _shifted_iterations;
+  std::vector<double> _shifted_res;
+  std::vector<int> _shifted_stopped;
   std::shared_ptr<cgx_mixed> _mixed;
   cgx_csr *_mixed_for = nullptr;
   // what the inner solver was last given (setting either drops its captured graphs)

@@ -484,6 +484,71 @@ int cgx_cg_set_batch_form(cgx_cg *cg, int form);
  * in effect). */
 int cgx_cg_batch_info(cgx_cg *cg, int *form_in_effect, int *width);
 
+/* ---- multi-shift CG: one matrix under several diagonal shifts (replaces
+ * nothing in the reference, whose solve takes one matrix) -------
+ * cgx_cg_solve_shifted solves (A + sigma_s I) x_s = b for nshift (1..8) shifts
+ * sigma_s >= 0 from x_s = 0 in one Krylov space: the shifted residuals stay
+ * collinear with the base residual of A, r_s = zeta_s r, so one SpMV and one
+ * pair of dots per body serve every shift and a shift costs its own x_s and
+ * p_s update (32 N bytes per body). The body is three launches (the mode-1
+ * shape, whatever the solver's mode; graph-replayed in chunks of the poll
+ * interval, cgx_cg_config): the SpMV with p.Ap and the r update of the single
+ * solver, unchanged, in every SpMV format, then one launch with the base p
+ * update and every active shift's updates. Scalars stay on the device.
+ * The base recurrence is the mode-1 loop on A from x = 0 (it keeps no x): in
+ * body n, a = alpha_n = rxr / pAp and bt = beta_n = rr / rxr as cgx_cg_solve
+ * forms them; ap = alpha_{n-1}, bp = beta_{n-1} (1 and 0 in body 0). A shift
+ * keeps zc = zeta_n and zp = zeta_{n-1} (1 and 1 in body 0), p_s = b, x_s = 0.
+ * After r is updated an active shift runs, in f64, every operation rounded
+ * and none contracted, the parentheses being the order:
+ *   t1 = (a * bp) * (zp - zc)
+ *   t2 = (zp * ap) * (1 + sigma * a)
+ *   zn = ((zc * zp) * ap) / (t1 + t2)
+ *   q  = zn / zc ;  as = a * q ;  bs = (bt * q) * q
+ *   x_s[i] = x_s[i] + as * p_s[i]
+ *   p_s[i] = zn * r[i] + bs * p_s[i]              (r is r_{n+1})
+ *   zp = zc ; zc = zn
+ * and the base does p = r + bt * p. With sigma = 0 and finite scalars zn = 1,
+ * as = a and bs = bt exactly: that column is cgx_cg_solve in mode 1 from
+ * x0 = 0, bit for bit (x, bodies, stop code).
+ * Freeze rule (Q5 on the shift's own residual norm |zeta_s| ||r|| at the start
+ * of the body): in body n, with m = bodies + 1, an active shift has
+ *   stop = isnan(rxr_n) || fabs(zc) * sqrt(rxr_n) <= tol || !(fabs(zn) >= DBL_MIN)
+ * bodies_s = m; stop -> code 1 and the shift is frozen from the next body on;
+ * else m >= cap -> code 2. (The third term freezes a shift whose zeta left the
+ * normal range: its residual is below DBL_MIN ||r||.) Later bodies neither
+ * read nor write a frozen shift's x_s and p_s. The solve goes on while any
+ * shift is active and m < cap = min(N + 1, max_bodies) (N + 1 when
+ * max_bodies < 0). With a base scalar that is not finite the body counts and
+ * codes are the single solve's (the NaN rule ends every shift) and the values
+ * of x_s are unspecified.
+ * Blocking. d_X (output only, column-major, ldx >= n; elements [n, ldx) of a
+ * column are not touched; a column that is not 16-byte aligned, from an odd
+ * ldx, takes 8-byte accesses). bodies_out[nshift]; res_out[nshift] =
+ * fabs(zeta_s) * sqrt(r.r) after the shift's last body; stopped_out[nshift]
+ * (may be NULL; 1 frozen by the rule, 2 cap reached). Duplicate shifts are
+ * allowed. CGX_EINVAL for nshift outside 1..8, a NULL pointer, ldx < n, and a
+ * shift that is negative or not finite (A + sigma I must stay SPD, and for
+ * sigma >= 0 every shift's residual is bounded by the base's).
+ * CGX_EUNSUPPORTED, the reason named, on an f32 solver, on a partitioned
+ * matrix and with a diagonal or block preconditioner set (M (A + sigma I) is
+ * not a shift of M A). The call ends a single solve or a batch in progress;
+ * cgx_cg_begin and the batch calls end it. The auto choices never pick it.
+ * The shifts' buffers (one p_s of n + 2 doubles per shift, the state) are
+ * allocated on first use and freed by cgx_cg_destroy.
+ * One shift alone carries a second direction vector on top of the single
+ * solve's body and loses to cgx_cg_solve on the shifted matrix: 1.08 to 1.17
+ * of a mode-1 body on an MI355X; from two shifts on it wins, 0.57 to 0.73 at
+ * two and 0.20 to 0.44 at eight of as many mode-1 bodies
+ * (tools/shift_bench.py, profiles/shift_bench.log).
+ * cgx_cg_shifted_zeta: zeta_s after each shift's last body of the last
+ * shifted solve (CGX_ESTATE before any). */
+enum { CGX_SHIFT_MAX = 8 };
+int cgx_cg_solve_shifted(cgx_cg *cg, int nshift, const double *h_sigma, const void *d_b,
+                         void *d_X, int64_t ldx, double tol, int64_t max_bodies,
+                         int64_t *bodies_out, double *res_out, int *stopped_out);
+int cgx_cg_shifted_zeta(cgx_cg *cg, double *zeta_out /* [nshift] */);
+
 /* ---- cgx_mixed: an f64 system solved with f32 bodies (replaces nothing in
  * the reference, whose solve runs in one precision) -----------
  * Iterative refinement: A x = b in f64 is solved to `tol` on the TRUE f64
