@@ -37,6 +37,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "cgx_block_inv.h"
 #include "cgx_dd.h"
 #include "cgx_internal.h"
 #include "cgx_objects.h"
@@ -6237,9 +6238,6 @@ __global__ __launch_bounds__(kBlock) void k_update_p_defer_pc(
 // matrix, and rows are short; a row too long for that costs one slow thread,
 // not a wrong value. bad[0] counts the rows whose diagonal is missing, not
 // positive or not finite, bad[1] keeps the lowest such row.
-template <typename T> __device__ __forceinline__ bool pc_ok(T d) {
-  return d > T(0) && d <= std::numeric_limits<T>::max();  // false for NaN
-}
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_diag_inv(int64_t n, const int *__restrict__ rowptr,
                                                      const int *__restrict__ col,
@@ -6291,12 +6289,10 @@ constexpr int kGridUpdateRBlk = 512;
 // rows of a tile of k_update_r_blk: whole blocks only
 __host__ __device__ constexpr int blk_tile_rows(int bs) { return (kBlkTile / bs) * bs; }
 
-// W_b = (diagonal block b of A)^-1 by LDL^T without pivoting, statement for
-// statement tests/bj_model.py block_inverse. One thread per block. Row i of
-// the block takes the entries of CSR row i with b0 <= col <= i (the lower
-// triangle decides; duplicates summed from 0 in entry order; rows may be
-// unsorted). A pivot that is not positive and finite makes the block bad:
-// bad[0] counts such blocks, bad[1] keeps the lowest one's index.
+// W_b = (diagonal block b of A)^-1 by LDL^T without pivoting: block_inv_one
+// (cgx_block_inv.h), one thread per block. A pivot that is not positive and
+// finite makes the block bad: bad[0] counts such blocks, bad[1] keeps the
+// lowest one's index.
 template <int BS>
 __global__ __launch_bounds__(kBlock) void k_block_inv(int64_t n, const int *__restrict__ rowptr,
                                                       const int *__restrict__ col,
@@ -6308,73 +6304,7 @@ __global__ __launch_bounds__(kBlock) void k_block_inv(int64_t n, const int *__re
   for (int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x; b < nb; b += stride) {
     const int64_t b0 = b * BS;
     const int m = (int)min((int64_t)BS, n - b0);  // rows of this block
-    double B[BS][BS], L[BS][BS], M[BS][BS], D[BS], E[BS];
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-#pragma unroll
-      for (int j = 0; j <= i; ++j) B[i][j] = 0.0;
-      if (i < m) {
-        for (int k = rowptr[b0 + i]; k < rowptr[b0 + i + 1]; ++k) {
-          const int64_t c = (int64_t)col[k] - b0;
-          const double v = val[k];
-#pragma unroll
-          for (int j = 0; j <= i; ++j)
-            if (c == j) B[i][j] = B[i][j] + v;
-        }
-      }
-    }
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < BS; ++j) {
-      if (j < m) {
-        double s = B[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) s = s - L[j][k] * (L[j][k] * D[k]);
-        D[j] = s;
-        if (!pc_ok(s)) ok = false;
-#pragma unroll
-        for (int i = j + 1; i < BS; ++i) {
-          if (i < m) {
-            double t = B[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) t = t - L[i][k] * (L[j][k] * D[k]);
-            L[i][j] = t / s;
-          }
-        }
-        E[j] = 1.0 / s;
-      }
-    }
-    // M = L^-1 (unit lower triangle): M[i][j] = -(L[i][j] + sum_{j<k<i} L[i][k] M[k][j])
-#pragma unroll
-    for (int i = 1; i < BS; ++i) {
-      if (i < m) {
-#pragma unroll
-        for (int j = 0; j < i; ++j) {
-          double s = L[i][j];
-#pragma unroll
-          for (int k = j + 1; k < i; ++k) s = s + L[i][k] * M[k][j];
-          M[i][j] = -s;
-        }
-      }
-    }
-    // W = M^T D^-1 M, the lower triangle computed and mirrored
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-      if (i < m) {
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-          double s = j == i ? E[i] : M[i][j] * E[i];
-#pragma unroll
-          for (int k = i + 1; k < BS; ++k)
-            if (k < m) s = s + (M[k][i] * E[k]) * (j == i ? M[k][i] : M[k][j]);
-          out[(b0 + i) * BS + j] = s;
-          out[(b0 + j) * BS + i] = s;
-        }
-#pragma unroll
-        for (int j = 0; j < BS; ++j)
-          if (j >= m) out[(b0 + i) * BS + j] = 0.0;
-      }
-    }
+    const bool ok = block_inv_one<BS, int64_t>(rowptr, col, val, out, b0, m);
     if (!ok) {
       atomicAdd(&bad[0], 1ull);
       atomicMin(&bad[1], (unsigned long long)b);
@@ -6383,7 +6313,7 @@ __global__ __launch_bounds__(kBlock) void k_block_inv(int64_t n, const int *__re
 }
 
 // a caller's W: every entry of a real column finite, every W_b[i, i] positive
-// and finite (pc_ok). bad[0] counts the rows that fail, bad[1] the lowest.
+// and finite (block_row_ok). bad[0] counts the rows that fail, bad[1] the lowest.
 __global__ __launch_bounds__(kBlock) void k_block_check(int64_t n, int bs,
                                                         const double *__restrict__ W,
                                                         unsigned long long *bad) {
@@ -6391,12 +6321,7 @@ __global__ __launch_bounds__(kBlock) void k_block_check(int64_t n, int bs,
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
     const int64_t b0 = (i / bs) * bs;
     const int nc = (int)min((int64_t)bs, n - b0);
-    bool ok = pc_ok(W[i * bs + (i - b0)]);
-    for (int j = 0; j < nc; ++j) {
-      const double w = W[i * bs + j];
-      if (!(fabs(w) <= std::numeric_limits<double>::max())) ok = false;  // NaN, Inf
-    }
-    if (!ok) {
+    if (!block_row_ok(W + i * bs, (int)(i - b0), nc)) {
       atomicAdd(&bad[0], 1ull);
       atomicMin(&bad[1], (unsigned long long)i);
     }

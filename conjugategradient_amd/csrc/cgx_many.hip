@@ -14,8 +14,9 @@
 // stop rule Q5 as k_update_xp applies it. With cgx_many_set_precond the same
 // kernel runs PCG with a diagonal M^-1 (kManyDiag), pinned the same way
 // to mode 1 under cgx_cg_set_precond. For n <= 256 k_many_cg_wave gives each
-// system a wave instead (cgx_many_set_form): the same arithmetic, four
-// independent solves per workgroup and no workgroup barrier. With
+// system a wave instead (cgx_many_set_form): the same function
+// (many_cg_body) run by another team, four independent solves per workgroup
+// and no workgroup barrier. With
 // cgx_many_set_block_precond both forms run PCG with dense diagonal blocks of
 // 1 to 8 rows (kManyBlock), pinned to mode 1 under cgx_cg_set_block_precond;
 // the blocks' inverses come from a launch of their own (k_many_block_inv).
@@ -26,6 +27,7 @@
 #include <mutex>
 #include <type_traits>
 
+#include "cgx_block_inv.h"
 #include "cgx_dd.h"
 #include "cgx_objects.h"
 
@@ -67,11 +69,6 @@ enum ManyPc {
   kManyDiag = 1,   // z = m o r (cgx_many_set_precond)
   kManyBlock = 2   // z = blockdiag(W_b) r (cgx_many_set_block_precond)
 };
-
-// k_diag_inv's verdict on a diagonal (or on a caller's m): positive and finite
-__device__ __forceinline__ bool many_pc_ok(double d) {
-  return d > 0.0 && d <= std::numeric_limits<double>::max();  // false for NaN
-}
 
 // The workgroup sum of one pair per thread, rounded once, in every thread:
 // waves first (wave_sum_dd), then wave 0 to 3 in that order, as
@@ -182,261 +179,6 @@ __device__ __forceinline__ void many_block_sweep(const double *__restrict__ Ws, 
   }
 }
 
-// R rows per thread: n <= R kBlock. LDS: p (R kBlock doubles) and two
-// reduction stagings.
-//
-// kManyDiag: diagonal preconditioning (cgx_many_set_precond), statement for statement
-// as k_pc_init, update_r_pc_body, k_update_xp_pc and pc_stop_rule
-// (cgx_kernels.hip): z_i = m_i * r_i, rounded, never stored beyond the body
-// that forms it (it takes Ap's register once r is updated); alpha = rz / p.Ap,
-// beta = rz' / rz, r.r and r.z summed behind one barrier, so a body keeps its
-// three barriers; the stop rule tests the true r.r. m is a second R kBlock
-// doubles of LDS that a thread reads and writes only at its own rows (stride
-// 1, no barrier of its own): a.M's entries (DIAGONAL), or 1 / a_ii formed by
-// the row's thread from the values this solve reads (JACOBI, a.M == NULL; the
-// entries with col == row summed from 0 in entry order, as k_diag_inv), so a
-// caller who overwrites the values in place never meets a stale diagonal.
-// A row without a diagonal entry (JACOBI), or a d (JACOBI) or m_i (DIAGONAL)
-// that is not positive and finite, ends that system before anything of it is
-// written: X as given, 0 bodies, NaN r.r and r.z, stop code 3. `refused`
-// carries the verdict across the init's first barrier; the extra barrier of
-// that path keeps a thread that is already at the next system from writing
-// the word while another still reads it. The plain form (kManyPlain) is the
-// code it was: every addition is behind `if constexpr`.
-//
-// kManyBlock: block-Jacobi preconditioning (cgx_many_set_block_precond),
-// statement for statement as k_pc_init_blk and update_r_blk_body. A block's
-// rows belong to different threads (a block across a multiple of kBlock wraps
-// from thread 255 to thread 0), so the updated r goes through LDS: mm is the
-// r staging here (there is no m), published by the barrier of the r.r sum;
-// each thread then forms z for its own rows from its row of W_s (bs
-// contiguous doubles, read from memory every body) and the block's r, keeps
-// it where Ap was, and r.z is a third sum: four barriers a body. The sums use
-// three stagings, red[0][0..8) for p.Ap, red[1][0..8) for r.r and
-// red[1][8..16) for r.z, each written once a body, so many_sum's rule holds.
-// A bad system's verdict comes from the launch before this one (stopped[s]): its
-// address is uniform, so is the `continue`, and nothing of that system is
-// touched but its four outputs.
-template <int R, ManyPc PC>
-__global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
-  constexpr bool DG = PC == kManyDiag, BK = PC == kManyBlock, PCD = PC != kManyPlain;
-  __shared__ double p[R * kBlock];
-  __shared__ double red[2][PCD ? 16 : 8];
-  // (unused, and dropped, in the plain form; the block form's staged r, read past its end)
-  __shared__ double mm[PCD ? R * kBlock + (BK ? kManyStagePad : 0) : 1];
-  __shared__ int refused;                      // (the same; the diagonal form's alone)
-  const int t = threadIdx.x, n = a.n;
-  if constexpr (DG) {
-    if (t == 0) refused = 0;
-    __syncthreads();
-  }
-  // the pattern is every system's: a thread's row bounds stay in registers
-  int e0[R], e1[R];
-#pragma unroll
-  for (int k = 0; k < R; ++k) {
-    const int i = t + k * kBlock;
-    e0[k] = i < n ? a.rowptr[i] : 0;
-    e1[k] = i < n ? a.rowptr[i + 1] : 0;
-  }
-  for (int s = blockIdx.x; s < a.nsys; s += gridDim.x) {
-    const double *__restrict__ val = a.val + (int64_t)s * a.ldv;
-    const double *__restrict__ b = a.B + (int64_t)s * a.ldb;
-    double *__restrict__ xs = a.X + (int64_t)s * a.ldx;
-    if constexpr (BK) {
-      if (a.stopped[s] != 0) {  // the verdict; uniform: one address for the workgroup
-        if (t == 0) {
-          a.bodies[s] = 0;
-          a.rxr[s] = __builtin_nan("");
-          a.rz[s] = __builtin_nan("");
-          a.stopped[s] = 3;
-        }
-        continue;
-      }
-    }
-    double x[R], r[R];
-    // ---- init: r = b - A x, p = r, rxr = r.r (k_cg_init) ----
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int i = t + k * kBlock;
-      x[k] = i < n ? xs[i] : 0.0;
-      if (i < n) p[i] = x[k];  // x through LDS: the init's gather source
-    }
-    if constexpr (DG) {  // m of the own rows, and the verdict on it
-      bool bad = false;
-#pragma unroll
-      for (int k = 0; k < R; ++k) {
-        const int i = t + k * kBlock;
-        if (i < n) {
-          double mv;
-          if (a.M) {
-            mv = a.M[(int64_t)s * a.ldm + i];
-            bad = bad || !many_pc_ok(mv);
-          } else {
-            double d = 0.0;
-            bool found = false;
-            for (int e = e0[k]; e < e1[k]; ++e)
-              if (a.col[e] == i) {
-                d = d + val[e];
-                found = true;
-              }
-            mv = 1.0 / d;
-            bad = bad || !found || !many_pc_ok(d);
-          }
-          mm[i] = mv;
-        }
-      }
-      if (bad) refused = s + 1;  // (s + 1 > 0 marks this system alone: no reset)
-    }
-    __syncthreads();
-    if constexpr (DG) {
-      if (refused == s + 1) {  // uniform: every thread reads it behind the barrier
-        if (t == 0) {
-          a.bodies[s] = 0;
-          a.rxr[s] = __builtin_nan("");
-          a.rz[s] = __builtin_nan("");
-          a.stopped[s] = 3;
-        }
-        __syncthreads();  // every read of `refused`, before the next system may write it
-        continue;
-      }
-    }
-    Dd<double> acc(0.0);
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int i = t + k * kBlock;
-      double sum = 0.0;
-      for (int e = e0[k]; e < e1[k]; ++e) sum = sum + val[e] * p[a.col[e]];
-      r[k] = 0.0;
-      if (i < n) {
-        r[k] = b[i] - sum;
-        acc += r[k] * r[k];
-        if constexpr (BK) mm[i] = r[k];  // staged for the blocks' other rows
-      }
-    }
-    __syncthreads();  // every gather of x is done: p may be overwritten
-    double rxr, rz = 0.0;
-    if constexpr (BK) {  // p = z = M^-1 r, rz = r.z (k_pc_init_blk)
-      Dd<double> accz(0.0);
-      double z0[R];
-      many_block_sweep<R, kBlock>(a.M + (int64_t)s * a.ldm, a.bs, t, n, mm, r, z0, accz, p);
-      many_sum2(acc, accz, red[1], &rxr, &rz);  // (its barrier publishes p too)
-    } else if constexpr (DG) {  // p = m o r, rz = r.(m o r) (k_pc_init)
-      Dd<double> accz(0.0);
-#pragma unroll
-      for (int k = 0; k < R; ++k) {
-        const int i = t + k * kBlock;
-        if (i < n) {
-          const double z = mm[i] * r[k];
-          p[i] = z;
-          accz += r[k] * z;
-        }
-      }
-      many_sum2(acc, accz, red[1], &rxr, &rz);  // (its barrier publishes p too)
-    } else {
-#pragma unroll
-      for (int k = 0; k < R; ++k) {
-        const int i = t + k * kBlock;
-        if (i < n) p[i] = r[k];
-      }
-      rxr = many_sum(acc, red[1]);  // (its barrier publishes p too)
-    }
-    long long bodies = 0;
-    int stopped = 0;
-    // ---- the bodies ----
-    for (;;) {
-      // Ap = A p and p.Ap (k_spmv_dot)
-      double Ap[R];
-      acc = Dd<double>(0.0);
-#pragma unroll
-      for (int k = 0; k < R; ++k) {
-        const int i = t + k * kBlock;
-        double sum = 0.0;
-        for (int e = e0[k]; e < e1[k]; ++e) sum = sum + val[e] * p[a.col[e]];
-        Ap[k] = sum;
-        if (i < n) acc += sum * p[i];
-      }
-      const double pAp = many_sum(acc, red[0]);
-      const double alpha = (PCD ? rz : rxr) / pAp;
-      // r -= alpha Ap and r.r (k_update_r); PC: r.z in the same sweep, z
-      // kept where Ap was (update_r_pc_body)
-      acc = Dd<double>(0.0);
-      double rr, rzn = 0.0;
-      if constexpr (BK) {  // (update_r_blk_body)
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-          const int i = t + k * kBlock;
-          if (i < n) {
-            r[k] = r[k] - alpha * Ap[k];
-            acc += r[k] * r[k];
-            mm[i] = r[k];
-          }
-        }
-        rr = many_sum(acc, red[1]);  // (its barrier publishes the staged r too)
-        Dd<double> accz(0.0);
-        many_block_sweep<R, kBlock>(a.M + (int64_t)s * a.ldm, a.bs, t, n, mm, r, Ap, accz,
-                                    nullptr);
-        rzn = many_sum(accz, red[1] + 8);
-      } else if constexpr (DG) {
-        Dd<double> accz(0.0);
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-          const int i = t + k * kBlock;
-          if (i < n) {
-            r[k] = r[k] - alpha * Ap[k];
-            acc += r[k] * r[k];
-            const double z = mm[i] * r[k];
-            accz += r[k] * z;
-            Ap[k] = z;
-          }
-        }
-        many_sum2(acc, accz, red[1], &rr, &rzn);
-      } else {
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-          const int i = t + k * kBlock;
-          if (i < n) {
-            r[k] = r[k] - alpha * Ap[k];
-            acc += r[k] * r[k];
-          }
-        }
-        rr = many_sum(acc, red[1]);
-      }
-      const double beta = PCD ? rzn / rz : rr / rxr;
-      // x += alpha p; p = r + beta p (PC: m o r + beta p); the stop rule
-      // (k_update_xp, k_update_xp_pc). Every gather of this body's p lies
-      // before the two barriers above.
-#pragma unroll
-      for (int k = 0; k < R; ++k) {
-        const int i = t + k * kBlock;
-        if (i < n) {
-          const double pv = p[i];
-          x[k] = x[k] + alpha * pv;
-          p[i] = (PCD ? Ap[k] : r[k]) + beta * pv;
-        }
-      }
-      ++bodies;
-      const bool cond = isnan(rxr) || sqrt(rxr) <= a.tol;  // Q5: the r.r the body began with
-      const bool cont = !cond && bodies < a.cap;
-      stopped = cond ? 1 : (cont ? 0 : 2);
-      rxr = rr;
-      if constexpr (PCD) rz = rzn;
-      __syncthreads();  // the new p, before the next gather (or the next system's x)
-      if (!cont) break;
-    }
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int i = t + k * kBlock;
-      if (i < n) xs[i] = x[k];
-    }
-    if (t == 0) {
-      a.bodies[s] = bodies;
-      a.rxr[s] = rxr;
-      a.stopped[s] = stopped;
-      if constexpr (PCD) a.rz[s] = rz;
-    }
-  }
-}
-
 // ---- a wave per system (n <= 256; cgx_many_set_form) --------
 constexpr int kWave = 64;
 constexpr int kWaves = kBlock / kWave;  // systems a workgroup runs side by side
@@ -466,43 +208,132 @@ __device__ __forceinline__ double wave_dot(Dd<double> v) {
   return wave_first(wave_sum_dd(v).value());
 }
 
-// R rows per lane: n <= R kWave. Wave w of workgroup b runs systems 4 b + w,
-// 4 b + w + 4 grid, ...; lane l owns rows l, l + 64, ...: their x and r in
-// registers, p (and m, or the block form's staged r) in the wave's own LDS. The
-// four waves of a workgroup never meet: there is no workgroup barrier below
-// (they run different body counts, so one would hang), only wave_order()
-// where k_many_cg has a barrier. The arithmetic is k_many_cg's, statement for
-// statement; a bad diagonal's verdict is a wave vote.
-template <int R, ManyPc PC>
-__global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
+// ---- the team that runs one system -----------------------------------------
+// What many_cg_body asks of the threads that share a system: who I am (me; my
+// rows are me, me + S, ...), which systems the team takes (first, step), what
+// separates an LDS write from its read by another thread (sync where both forms
+// need a point, order where a workgroup sum's barrier already serves), how a
+// dot is summed (sum, sum2; red + at: the staging, which only the workgroup
+// uses) and how a bad diagonal's verdict reaches every thread (vote).
+
+// A workgroup per system: kBlock threads, R kBlock rows, workgroup barriers.
+struct TeamWg {
+  static constexpr int S = kBlock;
+  static __device__ __forceinline__ int me() { return threadIdx.x; }
+  static __device__ __forceinline__ int first() { return blockIdx.x; }
+  static __device__ __forceinline__ int step() { return gridDim.x; }
+  static __device__ __forceinline__ void sync() { __syncthreads(); }
+  static __device__ __forceinline__ void order() {}
+  static __device__ __forceinline__ double sum(Dd<double> v, double *red, int at) {
+    return many_sum(v, red + at);
+  }
+  static __device__ __forceinline__ void sum2(Dd<double> u, Dd<double> v, double *red, int at,
+                                              double *su, double *sv) {
+    many_sum2(u, v, red + at, su, sv);
+  }
+  // `refused` carries the verdict across the barrier (s + 1 > 0 marks this
+  // system alone: no reset). A refused system's path has a sync() of its own,
+  // which keeps a thread that is already at the next system from writing the
+  // word while another still reads it.
+  static __device__ __forceinline__ bool vote(bool bad, int s, int *refused) {
+    if (bad) *refused = s + 1;
+    __syncthreads();
+    return *refused == s + 1;  // uniform: every thread reads it behind the barrier
+  }
+};
+
+// A wave per system: wave w of workgroup b runs systems 4 b + w, 4 b + w +
+// 4 grid, ...; 64 lanes, R kWave rows, p (and m, or the block form's staged r)
+// in the wave's own part of the LDS. The four waves of a workgroup never meet:
+// there is no workgroup barrier (they run different body counts, so one would
+// hang), only wave_order().
+struct TeamWave {
+  static constexpr int S = kWave;
+  static __device__ __forceinline__ int wave() {  // (a scalar: the compiler sees it uniform)
+    return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  }
+  static __device__ __forceinline__ int me() { return threadIdx.x & (kWave - 1); }
+  static __device__ __forceinline__ int first() { return blockIdx.x * kWaves + wave(); }
+  static __device__ __forceinline__ int step() { return gridDim.x * kWaves; }
+  static __device__ __forceinline__ void sync() { wave_order(); }
+  static __device__ __forceinline__ void order() { wave_order(); }
+  static __device__ __forceinline__ double sum(Dd<double> v, double *, int) { return wave_dot(v); }
+  static __device__ __forceinline__ void sum2(Dd<double> u, Dd<double> v, double *, int,
+                                              double *su, double *sv) {
+    *su = wave_dot(u);
+    *sv = wave_dot(v);
+  }
+  static __device__ __forceinline__ bool vote(bool bad, int, int *) {
+    const bool any = __any(bad);  // uniform: the wave's vote
+    wave_order();
+    return any;
+  }
+};
+
+// a system that is not solved: X as given, 0 bodies, NaN r.r and r.z, stop code 3
+__device__ __forceinline__ void many_refuse(const ManyArgs &a, int s) {
+  a.bodies[s] = 0;
+  a.rxr[s] = __builtin_nan("");
+  a.rz[s] = __builtin_nan("");
+  a.stopped[s] = 3;
+}
+
+// The solve, once for both forms: the team's systems one after another, each
+// from init to its last body. R rows per thread: n <= R Team::S. p: R Team::S
+// doubles of LDS, the gather source. red: the workgroup's reduction stagings.
+//
+// kManyDiag: diagonal preconditioning (cgx_many_set_precond), statement for statement
+// as k_pc_init, update_r_pc_body, k_update_xp_pc and pc_stop_rule
+// (cgx_kernels.hip): z_i = m_i * r_i, rounded, never stored beyond the body
+// that forms it (it takes Ap's register once r is updated); alpha = rz / p.Ap,
+// beta = rz' / rz, r.r and r.z summed behind one barrier, so a body keeps its
+// three barriers; the stop rule tests the true r.r. m (mm) is a second R
+// Team::S doubles of LDS that a thread reads and writes only at its own rows
+// (stride 1, no barrier of its own): a.M's entries (DIAGONAL), or 1 / a_ii
+// formed by the row's thread from the values this solve reads (JACOBI, a.M ==
+// NULL; the entries with col == row summed from 0 in entry order, as
+// k_diag_inv), so a caller who overwrites the values in place never meets a
+// stale diagonal. A row without a diagonal entry (JACOBI), or a d (JACOBI) or
+// m_i (DIAGONAL) that is not positive and finite, ends that system before
+// anything of it is written (many_refuse); the verdict is the team's vote.
+// The plain form (kManyPlain) has none of this: every addition is behind
+// `if constexpr`.
+//
+// kManyBlock: block-Jacobi preconditioning (cgx_many_set_block_precond),
+// statement for statement as k_pc_init_blk and update_r_blk_body. A block's
+// rows belong to different threads (a block across a multiple of Team::S wraps
+// from the last thread to thread 0), so the updated r goes through LDS: mm is
+// the r staging here (there is no m), published by the barrier of the r.r sum
+// (the wave form: by order()); each thread then forms z for its own rows from
+// its row of W_s (bs contiguous doubles, read from memory every body) and the
+// block's r, keeps it where Ap was, and r.z is a third sum: four barriers a
+// body. The sums use three stagings, red[0..8) for p.Ap, red[16..24) for r.r
+// and red[24..32) for r.z, each written once a body, so many_sum's rule holds.
+// A bad system's verdict comes from the launch before this one (stopped[s]): its
+// address is uniform, so is the `continue`, and nothing of that system is
+// touched but its four outputs.
+template <int R, ManyPc PC, class Team>
+__device__ __forceinline__ void many_cg_body(const ManyArgs &a, double *p, double *mm,
+                                             double *red, int *refused) {
   constexpr bool DG = PC == kManyDiag, BK = PC == kManyBlock, PCD = PC != kManyPlain;
-  __shared__ double p_all[kWaves * R * kWave];
-  // (unused, and dropped, in the plain form; the block form's staged r, read past its end)
-  __shared__ double m_all[PCD ? kWaves * R * kWave + (BK ? kManyStagePad : 0) : 1];
-  const int lane = threadIdx.x & (kWave - 1), n = a.n;
-  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  double *const p = p_all + w * (R * kWave);
-  [[maybe_unused]] double *const mm = m_all + (PCD ? w * (R * kWave) : 0);
-  // the pattern is every system's: a lane's row bounds stay in registers
+  constexpr int S = Team::S;
+  constexpr int kRed1 = PCD ? 16 : 8;  // the second staging's place in red
+  const int t = Team::me(), n = a.n;
+  // the pattern is every system's: a thread's row bounds stay in registers
   int e0[R], e1[R];
 #pragma unroll
   for (int k = 0; k < R; ++k) {
-    const int i = lane + k * kWave;
+    const int i = t + k * S;
     e0[k] = i < n ? a.rowptr[i] : 0;
     e1[k] = i < n ? a.rowptr[i + 1] : 0;
   }
-  for (int s = blockIdx.x * kWaves + w; s < a.nsys; s += gridDim.x * kWaves) {
+  for (int s = Team::first(); s < a.nsys; s += Team::step()) {
     const double *__restrict__ val = a.val + (int64_t)s * a.ldv;
     const double *__restrict__ b = a.B + (int64_t)s * a.ldb;
     double *__restrict__ xs = a.X + (int64_t)s * a.ldx;
     if constexpr (BK) {
-      if (a.stopped[s] != 0) {  // the verdict; uniform: one address for the wave
-        if (lane == 0) {
-          a.bodies[s] = 0;
-          a.rxr[s] = __builtin_nan("");
-          a.rz[s] = __builtin_nan("");
-          a.stopped[s] = 3;
-        }
+      if (a.stopped[s] != 0) {  // the verdict; uniform: one address for the team
+        if (t == 0) many_refuse(a, s);
         continue;
       }
     }
@@ -510,7 +341,7 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
     // ---- init: r = b - A x, p = r, rxr = r.r (k_cg_init) ----
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-      const int i = lane + k * kWave;
+      const int i = t + k * S;
       x[k] = i < n ? xs[i] : 0.0;
       if (i < n) p[i] = x[k];  // x through LDS: the init's gather source
     }
@@ -518,12 +349,12 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
       bool bad = false;
 #pragma unroll
       for (int k = 0; k < R; ++k) {
-        const int i = lane + k * kWave;
+        const int i = t + k * S;
         if (i < n) {
           double mv;
           if (a.M) {
             mv = a.M[(int64_t)s * a.ldm + i];
-            bad = bad || !many_pc_ok(mv);
+            bad = bad || !pc_ok(mv);
           } else {
             double d = 0.0;
             bool found = false;
@@ -533,26 +364,23 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
                 found = true;
               }
             mv = 1.0 / d;
-            bad = bad || !found || !many_pc_ok(d);
+            bad = bad || !found || !pc_ok(d);
           }
           mm[i] = mv;
         }
       }
-      if (__any(bad)) {  // uniform: the wave's vote
-        if (lane == 0) {
-          a.bodies[s] = 0;
-          a.rxr[s] = __builtin_nan("");
-          a.rz[s] = __builtin_nan("");
-          a.stopped[s] = 3;
-        }
-        continue;  // (p holds x, which nobody gathered: the next system overwrites it)
+      if (Team::vote(bad, s, refused)) {  // (its point is the one below: x is in p)
+        if (t == 0) many_refuse(a, s);
+        Team::sync();  // every read of the verdict, before the next system's
+        continue;      // (p holds x, which nobody gathered: the next system overwrites it)
       }
+    } else {
+      Team::sync();  // x is in p
     }
-    wave_order();  // x is in p
     Dd<double> acc(0.0);
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-      const int i = lane + k * kWave;
+      const int i = t + k * S;
       double sum = 0.0;
       for (int e = e0[k]; e < e1[k]; ++e) sum = sum + val[e] * p[a.col[e]];
       r[k] = 0.0;
@@ -562,36 +390,34 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
         if constexpr (BK) mm[i] = r[k];  // staged for the blocks' other rows
       }
     }
-    wave_order();  // every gather of x is done: p may be overwritten
+    Team::sync();  // every gather of x is done: p may be overwritten
     double rxr, rz = 0.0;
     if constexpr (BK) {  // p = z = M^-1 r, rz = r.z (k_pc_init_blk)
       Dd<double> accz(0.0);
       double z0[R];
-      many_block_sweep<R, kWave>(a.M + (int64_t)s * a.ldm, a.bs, lane, n, mm, r, z0, accz, p);
-      rxr = wave_dot(acc);
-      rz = wave_dot(accz);
+      many_block_sweep<R, S>(a.M + (int64_t)s * a.ldm, a.bs, t, n, mm, r, z0, accz, p);
+      Team::sum2(acc, accz, red, kRed1, &rxr, &rz);
     } else if constexpr (DG) {  // p = m o r, rz = r.(m o r) (k_pc_init)
       Dd<double> accz(0.0);
 #pragma unroll
       for (int k = 0; k < R; ++k) {
-        const int i = lane + k * kWave;
+        const int i = t + k * S;
         if (i < n) {
           const double z = mm[i] * r[k];
           p[i] = z;
           accz += r[k] * z;
         }
       }
-      rxr = wave_dot(acc);
-      rz = wave_dot(accz);
+      Team::sum2(acc, accz, red, kRed1, &rxr, &rz);
     } else {
 #pragma unroll
       for (int k = 0; k < R; ++k) {
-        const int i = lane + k * kWave;
+        const int i = t + k * S;
         if (i < n) p[i] = r[k];
       }
-      rxr = wave_dot(acc);
+      rxr = Team::sum(acc, red, kRed1);
     }
-    wave_order();  // p is written
+    Team::order();  // p is written (a workgroup sum's barrier publishes it too)
     long long bodies = 0;
     int stopped = 0;
     // ---- the bodies ----
@@ -601,13 +427,13 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
       acc = Dd<double>(0.0);
 #pragma unroll
       for (int k = 0; k < R; ++k) {
-        const int i = lane + k * kWave;
+        const int i = t + k * S;
         double sum = 0.0;
         for (int e = e0[k]; e < e1[k]; ++e) sum = sum + val[e] * p[a.col[e]];
         Ap[k] = sum;
         if (i < n) acc += sum * p[i];
       }
-      const double pAp = wave_dot(acc);
+      const double pAp = Team::sum(acc, red, 0);
       const double alpha = (PCD ? rz : rxr) / pAp;
       // r -= alpha Ap and r.r (k_update_r); PC: r.z in the same sweep, z
       // kept where Ap was (update_r_pc_body)
@@ -616,24 +442,23 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
       if constexpr (BK) {  // (update_r_blk_body)
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-          const int i = lane + k * kWave;
+          const int i = t + k * S;
           if (i < n) {
             r[k] = r[k] - alpha * Ap[k];
             acc += r[k] * r[k];
             mm[i] = r[k];
           }
         }
-        wave_order();  // the staged r is written
+        rr = Team::sum(acc, red, kRed1);
+        Team::order();  // the staged r is written (a workgroup sum's barrier publishes it too)
         Dd<double> accz(0.0);
-        many_block_sweep<R, kWave>(a.M + (int64_t)s * a.ldm, a.bs, lane, n, mm, r, Ap, accz,
-                                   nullptr);
-        rr = wave_dot(acc);
-        rzn = wave_dot(accz);
+        many_block_sweep<R, S>(a.M + (int64_t)s * a.ldm, a.bs, t, n, mm, r, Ap, accz, nullptr);
+        rzn = Team::sum(accz, red, kRed1 + 8);
       } else if constexpr (DG) {
         Dd<double> accz(0.0);
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-          const int i = lane + k * kWave;
+          const int i = t + k * S;
           if (i < n) {
             r[k] = r[k] - alpha * Ap[k];
             acc += r[k] * r[k];
@@ -642,26 +467,26 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
             Ap[k] = z;
           }
         }
-        rr = wave_dot(acc);
-        rzn = wave_dot(accz);
+        Team::sum2(acc, accz, red, kRed1, &rr, &rzn);
       } else {
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-          const int i = lane + k * kWave;
+          const int i = t + k * S;
           if (i < n) {
             r[k] = r[k] - alpha * Ap[k];
             acc += r[k] * r[k];
           }
         }
-        rr = wave_dot(acc);
+        rr = Team::sum(acc, red, kRed1);
       }
       const double beta = PCD ? rzn / rz : rr / rxr;
-      wave_order();  // every gather of this body's p is done
       // x += alpha p; p = r + beta p (PC: m o r + beta p); the stop rule
-      // (k_update_xp, k_update_xp_pc)
+      // (k_update_xp, k_update_xp_pc). Every gather of this body's p is done:
+      // in a workgroup it lies before the sums' barriers above.
+      Team::order();
 #pragma unroll
       for (int k = 0; k < R; ++k) {
-        const int i = lane + k * kWave;
+        const int i = t + k * S;
         if (i < n) {
           const double pv = p[i];
           x[k] = x[k] + alpha * pv;
@@ -674,21 +499,52 @@ __global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
       stopped = cond ? 1 : (cont ? 0 : 2);
       rxr = rr;
       if constexpr (PCD) rz = rzn;
-      wave_order();  // the new p, before the next gather (or the next system's x)
+      Team::sync();  // the new p, before the next gather (or the next system's x)
       if (!cont) break;
     }
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-      const int i = lane + k * kWave;
+      const int i = t + k * S;
       if (i < n) xs[i] = x[k];
     }
-    if (lane == 0) {
+    if (t == 0) {
       a.bodies[s] = bodies;
       a.rxr[s] = rxr;
       a.stopped[s] = stopped;
       if constexpr (PCD) a.rz[s] = rz;
     }
   }
+}
+
+// A workgroup per system. LDS: p (R kBlock doubles) and two reduction
+// stagings; preconditioned: m, or the block form's staged r, and wider
+// stagings; the diagonal form: the verdict word.
+template <int R, ManyPc PC>
+__global__ __launch_bounds__(kBlock) void k_many_cg(ManyArgs a) {
+  constexpr bool DG = PC == kManyDiag, BK = PC == kManyBlock, PCD = PC != kManyPlain;
+  __shared__ double p[R * kBlock];
+  __shared__ double red[2][PCD ? 16 : 8];
+  // (unused, and dropped, in the plain form; the block form's staged r, read past its end)
+  __shared__ double mm[PCD ? R * kBlock + (BK ? kManyStagePad : 0) : 1];
+  __shared__ int refused;                      // (the same; the diagonal form's alone)
+  if constexpr (DG) {
+    if (threadIdx.x == 0) refused = 0;
+    __syncthreads();
+  }
+  many_cg_body<R, PC, TeamWg>(a, p, mm, &red[0][0], &refused);
+}
+
+// A wave per system (n <= R kWave): the same function, four independent
+// solves per workgroup, each in its own part of the LDS.
+template <int R, ManyPc PC>
+__global__ __launch_bounds__(kBlock) void k_many_cg_wave(ManyArgs a) {
+  constexpr bool BK = PC == kManyBlock, PCD = PC != kManyPlain;
+  __shared__ double p_all[kWaves * R * kWave];
+  // (unused, and dropped, in the plain form; the block form's staged r, read past its end)
+  __shared__ double m_all[PCD ? kWaves * R * kWave + (BK ? kManyStagePad : 0) : 1];
+  const int w = TeamWave::wave();
+  many_cg_body<R, PC, TeamWave>(a, p_all + w * (R * kWave), m_all + (PCD ? w * (R * kWave) : 0),
+                                nullptr, nullptr);
 }
 
 // The pattern's check, once at create: bad[0] counts the entries of rowptr
@@ -717,15 +573,11 @@ __global__ __launch_bounds__(kBlock) void k_many_check(int n, int nnz,
 
 // ---- block-Jacobi: the blocks' inverses (cgx_many_set_block_precond) -------
 // W_b = (diagonal block b of A_s)^-1 for every system s and block b, one thread
-// per (system, block): k_block_inv's statements (cgx_kernels.hip) restated,
-// which follow tests/bj_model.py block_inverse and csr_blocks one by one. Row
-// i of a block takes the entries of CSR row i with b0 <= col <= i (the lower
-// triangle decides; duplicates summed from 0 in entry order; rows may be
-// unsorted); LDL^T without pivoting; W = M^T D^-1 M with M = L^-1, the lower
-// triangle computed and mirrored; the columns past a partial last block +0.0.
-// System s's W is n x BS row-major at out + s ldw; [n BS, ldw) is not written.
-// A pivot that is not positive and finite (many_pc_ok) marks the system:
-// bad[s] = 1, atomically, and the block's W holds whatever the statements give.
+// per (system, block): block_inv_one (cgx_block_inv.h), the function k_block_inv
+// (cgx_kernels.hip) calls, here with int indices. System s's W is n x BS
+// row-major at out + s ldw; [n BS, ldw) is not written. A pivot that is not
+// positive and finite (pc_ok) marks the system: bad[s] = 1, atomically, and the
+// block's W holds whatever the statements give.
 template <int BS>
 __global__ __launch_bounds__(kBlock) void k_many_block_inv(int nsys, int n,
                                                            const int *__restrict__ rowptr,
@@ -741,80 +593,14 @@ __global__ __launch_bounds__(kBlock) void k_many_block_inv(int nsys, int n,
     const double *__restrict__ val = vals + (int64_t)s * ldv;
     double *__restrict__ out = outs + (int64_t)s * ldw;
     const int m = min(BS, n - b0);  // rows of this block
-    double B[BS][BS], L[BS][BS], M[BS][BS], D[BS], E[BS];
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-#pragma unroll
-      for (int j = 0; j <= i; ++j) B[i][j] = 0.0;
-      if (i < m) {
-        for (int k = rowptr[b0 + i]; k < rowptr[b0 + i + 1]; ++k) {
-          const int c = col[k] - b0;
-          const double v = val[k];
-#pragma unroll
-          for (int j = 0; j <= i; ++j)
-            if (c == j) B[i][j] = B[i][j] + v;
-        }
-      }
-    }
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < BS; ++j) {
-      if (j < m) {
-        double sj = B[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) sj = sj - L[j][k] * (L[j][k] * D[k]);
-        D[j] = sj;
-        if (!many_pc_ok(sj)) ok = false;
-#pragma unroll
-        for (int i = j + 1; i < BS; ++i) {
-          if (i < m) {
-            double tj = B[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) tj = tj - L[i][k] * (L[j][k] * D[k]);
-            L[i][j] = tj / sj;
-          }
-        }
-        E[j] = 1.0 / sj;
-      }
-    }
-    // M = L^-1 (unit lower triangle): M[i][j] = -(L[i][j] + sum_{j<k<i} L[i][k] M[k][j])
-#pragma unroll
-    for (int i = 1; i < BS; ++i) {
-      if (i < m) {
-#pragma unroll
-        for (int j = 0; j < i; ++j) {
-          double sj = L[i][j];
-#pragma unroll
-          for (int k = j + 1; k < i; ++k) sj = sj + L[i][k] * M[k][j];
-          M[i][j] = -sj;
-        }
-      }
-    }
-    // W = M^T D^-1 M, the lower triangle computed and mirrored
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-      if (i < m) {
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-          double sj = j == i ? E[i] : M[i][j] * E[i];
-#pragma unroll
-          for (int k = i + 1; k < BS; ++k)
-            if (k < m) sj = sj + (M[k][i] * E[k]) * (j == i ? M[k][i] : M[k][j]);
-          out[(b0 + i) * BS + j] = sj;
-          out[(b0 + j) * BS + i] = sj;
-        }
-#pragma unroll
-        for (int j = 0; j < BS; ++j)
-          if (j >= m) out[(b0 + i) * BS + j] = 0.0;
-      }
-    }
-    if (!ok) atomicOr(&bad[s], 1);
+    if (!block_inv_one<BS, int>(rowptr, col, val, out, b0, m)) atomicOr(&bad[s], 1);
   }
 }
 
-// A caller's W (CGX_BLOCK_GIVEN), one thread per (system, row), as
-// k_block_check: every entry of a real column finite, W_b[i, i] positive and
-// finite; a row that fails marks its system, bad[s] = 1, atomically.
+// A caller's W (CGX_BLOCK_GIVEN), one thread per (system, row), k_block_check's
+// verdict (block_row_ok, cgx_block_inv.h): every entry of a real column finite,
+// W_b[i, i] positive and finite; a row that fails marks its system, bad[s] = 1,
+// atomically.
 __global__ __launch_bounds__(kBlock) void k_many_block_check(int nsys, int n, int bs,
                                                              const double *__restrict__ Ws,
                                                              int64_t ldw, int *bad) {
@@ -825,10 +611,7 @@ __global__ __launch_bounds__(kBlock) void k_many_block_check(int nsys, int n, in
     const double *__restrict__ w = Ws + (int64_t)s * ldw + (int64_t)i * bs;
     const int b0 = (i / bs) * bs;
     const int nc = min(bs, n - b0);
-    bool ok = many_pc_ok(w[i - b0]);
-    for (int j = 0; j < nc; ++j)
-      if (!(fabs(w[j]) <= std::numeric_limits<double>::max())) ok = false;  // NaN, Inf
-    if (!ok) atomicOr(&bad[s], 1);
+    if (!block_row_ok(w, i - b0, nc)) atomicOr(&bad[s], 1);
   }
 }
 
@@ -941,26 +724,6 @@ void many_free(cgx_many *m) {
 ManyPc many_pc(const cgx_many *m) {
   if (m->blk_kind != CGX_BLOCK_NONE) return kManyBlock;
   return m->precond != CGX_PRECOND_NONE ? kManyDiag : kManyPlain;
-}
-
-template <ManyPc PC>
-void many_launch(int r, dim3 grid, dim3 block, hipStream_t s, const ManyArgs &a) {
-  switch (r) {
-    case 1: hipLaunchKernelGGL((k_many_cg<1, PC>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((k_many_cg<2, PC>), grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((k_many_cg<4, PC>), grid, block, 0, s, a); break;
-    case 8: hipLaunchKernelGGL((k_many_cg<8, PC>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((k_many_cg<16, PC>), grid, block, 0, s, a); break;
-  }
-}
-
-template <ManyPc PC>
-void many_launch_wave(int r, dim3 grid, dim3 block, hipStream_t s, const ManyArgs &a) {
-  switch (r) {
-    case 1: hipLaunchKernelGGL((k_many_cg_wave<1, PC>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((k_many_cg_wave<2, PC>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((k_many_cg_wave<4, PC>), grid, block, 0, s, a); break;
-  }
 }
 
 // Auto takes the wave form up to this many rows (0: never). See DESIGN.md §5e,
@@ -1171,6 +934,11 @@ extern "C" int cgx_many_solve(cgx_many *m, const void *d_B, int64_t ldb, void *d
   a.cap = (int)cap;
   const ManyPc kind = many_pc(m);
   const bool pc = kind != kManyPlain;
+  const bool wave = many_form(m) == CGX_MANY_FORM_WAVE;
+  const void *kernel = many_kernel(many_rows(m), kind, wave);
+  CGX_REQUIRE(kernel, CGX_EUNSUPPORTED,
+              "cgx_many_solve: no kernel is built for %d rows per %s (n %lld)", many_rows(m),
+              wave ? "lane" : "thread", (long long)n);
   a.M = m->precond == CGX_PRECOND_DIAGONAL ? m->d_M : nullptr;
   a.ldm = m->ldm;
   a.rz = m->d_rz;
@@ -1192,16 +960,8 @@ extern "C" int cgx_many_solve(cgx_many *m, const void *d_B, int64_t ldb, void *d
     }
   }
   const dim3 grid(many_grid(m)), block(kBlock);
-  if (many_form(m) == CGX_MANY_FORM_WAVE) {
-    if (kind == kManyBlock) many_launch_wave<kManyBlock>(many_rows(m), grid, block, s, a);
-    else if (pc) many_launch_wave<kManyDiag>(many_rows(m), grid, block, s, a);
-    else many_launch_wave<kManyPlain>(many_rows(m), grid, block, s, a);
-  } else {
-    if (kind == kManyBlock) many_launch<kManyBlock>(m->r, grid, block, s, a);
-    else if (pc) many_launch<kManyDiag>(m->r, grid, block, s, a);
-    else many_launch<kManyPlain>(m->r, grid, block, s, a);
-  }
-  CGX_HIP(hipGetLastError());
+  void *args[] = {&a};
+  CGX_HIP(hipLaunchKernel(kernel, grid, block, args, 0, s));
   const size_t ns = (size_t)m->nsys;
   if (pc) CGX_HIP(hipMemcpyAsync(m->h_rz, m->d_rz, ns * sizeof(double), hipMemcpyDeviceToHost, s));
   CGX_HIP(hipMemcpyAsync(m->h_bodies, m->d_bodies, ns * sizeof(long long), hipMemcpyDeviceToHost, s));

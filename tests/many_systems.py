@@ -96,6 +96,10 @@ def system_set(name):
         rp, cl, vals, B, tol, _, _ = system_set("multi")
         X0 = np.random.default_rng(43).standard_normal((5, B.shape[1]))
         return rp, cl, vals[:5].copy(), B[:5].copy(), tol, X0, 5
+    if name == "n1025x9":  # 8 rows per thread, which no size reaches: 9 systems, 41 x 25
+        rp, cl, vl = poisson2d(41, 25)
+        vals, B = variants(rp, cl, vl, 9, seed=1225, width=0.5)
+        return rp, cl, vals, B, _tol(B), None, -1
     if name.startswith("n"):  # the sizes: 3 systems each
         n = int(name[1:])
         rp, cl, vl = pattern_for(n)
@@ -122,4 +126,4 @@ def system_set(name):
     raise KeyError(name)
 
 
-ALL_SETS = ("multi", "multi5", "hub", "empty") + tuple(f"n{n}" for n in SIZES)
+ALL_SETS = ("multi", "multi5", "hub", "empty", "n1025x9") + tuple(f"n{n}" for n in SIZES)

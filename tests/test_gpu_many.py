@@ -16,7 +16,7 @@ entry order.
 Sizes: n = 1, 2 (fewer rows than a wave), 63 / 64 / 65 (the last partial wave
 of the 1-row-per-thread form), 255 / 256 / 257 (1 to 2 rows per thread), 1,023
 (4 rows per thread, a last stride of 255) and 4,096 (16 rows per thread, the
-most); 4,097 is refused.
+most); 4,097 is refused. 1,025 (8 rows per thread) has a test of its own.
 """
 import ctypes as C
 import os
@@ -167,6 +167,17 @@ def test_sizes(queue, n):
         out = m.solve(B, tol=tol)
         assert m.info()[1] == next(r for r in (1, 2, 4, 8, 16) if n <= 256 * r)
     assert_systems_equal(out, references(queue, name))
+    assert (out[3] == 1).all()
+
+
+def test_eight_rows_per_thread(queue):
+    """n = 1,025: k_many_cg<8, kManyPlain>, which no size above reaches; 9
+    systems, all on one workgroup."""
+    rp, cl, vals, B, tol, _, _ = M.system_set("n1025x9")
+    with Many(queue, rp, cl, vals) as m:
+        out = m.solve(B, tol=tol, max_workgroups=1)
+        assert m.info()[:2] == (1, 8)
+    assert_systems_equal(out, references(queue, "n1025x9"))
     assert (out[3] == 1).all()
 
 

@@ -251,6 +251,37 @@ def test_workgroup_form(queue, name, kind):
     assert (out[3] == (1 if mb < 0 else 2)).all()
 
 
+def test_eight_rows_per_thread(queue):
+    """n = 1,025, bs = 3 (a partial block of 2): k_many_cg<8, kManyBlock>, which
+    no set of many_block_systems reaches; 9 systems, all on one workgroup. The
+    set is built as many_block_systems.build builds its own, with the first
+    variants seed from 300 up (301) that leaves no dot of the model's runs
+    unclear, which is asserted here."""
+    from conjugategradient_amd.workloads import node_mixed
+    from tests import many_systems as M
+
+    bs, n, nsys = 3, 1025, 9
+    rp, cl, vl = S.cut(*node_mixed(19, 18, bs, S.E, 7), n)
+    vals, B = M.variants(rp, cl, vl, nsys, seed=301, width=0.25)
+    tol = M._tol(B)
+    refs = []
+    for s in range(nsys):
+        W, bad = bj_model.csr_block_inverse(rp, cl, vals[s], bs)
+        run = bj_model.cg(rp, cl, vals[s], B[s], tol, -1, W)
+        assert not bad and not run.unclear, s
+        ref = single(queue, rp, cl, vals[s], B[s], None, tol, -1, S.JACOBI, bs, None)
+        np.testing.assert_array_equal(ref[0], run.x, err_msg=f"system {s}: x")
+        np.testing.assert_array_equal(np.array([ref[1], ref[2], ref[4]]),
+                                      np.array([run.bodies, run.rr[-1], run.rz[-1]]))
+        refs.append(ref)
+    with BMany(queue, rp, cl, vals) as m:
+        m.set_block(S.JACOBI, bs)
+        out = m.psolve(B, tol=tol, max_workgroups=1)
+        assert m.info()[:2] == (1, 8)
+    assert_systems_equal(out, refs)
+    assert (out[3] == 1).all()
+
+
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("name", WAVE_SETS)
 def test_wave_form(queue, name, kind):

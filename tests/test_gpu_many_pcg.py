@@ -144,6 +144,18 @@ def test_sizes(queue, n, kind):
     assert tuple(nan_x) == P.NAN_X.get((name, kind), ())
 
 
+def test_eight_rows_per_thread(queue):
+    """n = 1,025: k_many_cg<8, kManyDiag>, which no size above reaches; 9
+    systems, all on one workgroup."""
+    rp, cl, vals, B, tol, _, _ = P.system_set("n1025x9")
+    with PMany(queue, rp, cl, vals) as m:
+        m.set("n1025x9", "jacobi")
+        out = m.psolve(B, tol=tol, max_workgroups=1)
+        assert m.info()[:2] == (1, 8)
+    assert_systems_equal(out, references(queue, "n1025x9", "jacobi"))
+    assert (out[3] == 1).all()
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_hub_row_against_the_model(queue, kind):
     rp, cl, vals, B, tol, _, _ = P.system_set("hub")
