@@ -410,33 +410,26 @@ template <typename T> int enqueue_iter(cgx_cg *cg, const CgView<T> &v, int slot)
   const int par = body_dir(cg, slot, 0), rpar = body_dir(cg, slot, 1),
             par3 = body_dir(cg, slot, 2);
   int npp = 0;
-  const PeerDev *far = fused_ar(cg);
-  const bool sep = A->dist && !far;  // a separate all-reduce step per dot
-  // preconditioned on a single device (cgx_cg_set_precond): the SpMV launch is
-  // the plain one. Partitioned: the plain partitioned body's
-  // steps, with the r.r all-reduce carrying r.z as its second value (tag
-  // base + 2)
-  const bool pc = cg->precond != CGX_PRECOND_NONE, pc_dist = pc && A->dist;
-  int np_rr = sep ? 0 : npr;  // the plain x/p update's r.r partials
-  // block-Jacobi (cgx_cg_set_block_precond; f64, one device, modes 1 and 3):
-  // the plain SpMV launch, update_r with z = M^-1 r stored over Ap, the p
-  // update reading z there
-  if constexpr (std::is_same_v<T, double>) {
-    if (cg->blk_kind != CGX_BLOCK_NONE) {
-      const double *W = (const double *)cg->blk_w;
-      const int bs = cg->blk_bs, npb = blk_update_parts(cg->n, bs);
-      if ((rc = enqueue_spmv_dot<T>(cg, v, p, slot, par, &npp))) return rc;
-      if ((rc = timed(cg, 2, s, [&] {
-             return blk_update_r(cg->n, bs, v.r, v.Ap, W, v.st, slot, v.ws, s, npp, rpar);
-           })))
-        return rc;
-      return timed(cg, 3, s, [&] {
-        if (defer)
-          return blk_update_p_defer(cg->n, v.x, p, pn, v.P, v.Ap, v.st, slot, v.ws, npb, s, par3);
-        return blk_update_xp(cg->n, v.x, p, v.Ap, v.st, slot, v.ws, npb, s, par3);
-      });
-    }
+  // The body's vector step, described once. The dots: partials on one device,
+  // all-reduced inside the kernels by the device peer transport (fused_ar),
+  // else a separate all-reduce step per dot into the scalar ring. z:
+  // preconditioned (cgx_cg_set_precond) the SpMV launch is the plain one and
+  // z = m o r is formed in the vector kernels; partitioned
+  // the plain partitioned body's steps, with the r.r all-reduce carrying r.z
+  // as its second value (tag base + 2). Block-Jacobi
+  // (cgx_cg_set_block_precond; f64, one device, modes 1 and 3): update_r
+  // stores z = M^-1 r over Ap, the p update reads z there.
+  VecStep<T> vs;
+  vs.peer = fused_ar(cg);
+  vs.ring = A->dist && !vs.peer;
+  const bool pc = cg->precond != CGX_PRECOND_NONE;
+  const bool blk = std::is_same_v<T, double> && cg->blk_kind != CGX_BLOCK_NONE;
+  if (pc) {
+    vs.m = v.m;
+    vs.m_nt = cg->minv_nt && !A->dist;
   }
+  if (blk) vs.z = v.Ap;
+  int np_rr = blk ? blk_update_parts(cg->n, cg->blk_bs) : npr;  // update_r's partials
   if (recomputes_ap(cg->mode)) {
     // mode 6: kernel 1 keeps only p.Ap, kernel 2 forms A p again and updates
     // r in the walk's epilogue (no Ap vector: 8 N bytes written and read
@@ -450,43 +443,30 @@ template <typename T> int enqueue_iter(cgx_cg *cg, const CgView<T> &v, int slot)
          })))
       return rc;
     np_rr = A->dev.vl_grid;
-    far = nullptr;
+    vs.peer = nullptr;
   } else {
     if ((rc = enqueue_spmv_dot<T>(cg, v, p, slot, par, &npp))) return rc;
-    if (sep && (rc = dist_dot<T>(cg, v, v.ws->pap_part, npp, &v.st->pAp[slot], slot, 1)))
+    if (vs.ring && (rc = dist_dot<T>(cg, v, v.ws->pap_part, npp, &v.st->pAp[slot], slot, 1)))
       return rc;
     if ((rc = timed(cg, 2, s, [&] {
-           if (pc_dist)
-             return Launch<T>::update_r_pc_dist(cg->n, v.r, v.Ap, v.m, v.st, slot, v.ws, s, npp,
-                                                rpar, far);
-           if (pc)
-             return Launch<T>::update_r_pc(cg->n, v.r, v.Ap, v.m, v.st, slot, v.ws, s, npp, rpar,
-                                           cg->minv_nt);
-           return Launch<T>::update_r(cg->n, v.r, v.Ap, v.st, slot, v.ws, s, false,
-                                      sep ? 0 : npp, rpar, nullptr, 0, far);
+           if constexpr (std::is_same_v<T, double>) {
+             if (blk)
+               return blk_update_r(cg->n, cg->blk_bs, v.r, v.Ap, (const double *)cg->blk_w, v.st,
+                                   slot, v.ws, s, npp, rpar);
+           }
+           return Launch<T>::update_r(cg->n, v.r, v.Ap, v.st, slot, v.ws, s, false, npp, rpar,
+                                      nullptr, 0, vs);
          })))
       return rc;
-    if (sep && (rc = pc_dist ? dist_dot_pair<T>(cg, v, npr, slot)
-                             : dist_dot<T>(cg, v, v.ws->rr_part, npr, &v.st->rr[slot], slot, 2)))
+    if (vs.ring && (rc = pc ? dist_dot_pair<T>(cg, v, npr, slot)
+                            : dist_dot<T>(cg, v, v.ws->rr_part, npr, &v.st->rr[slot], slot, 2)))
       return rc;
   }
   return timed(cg, 3, s, [&] {
-    if (defer && pc_dist)
-      return Launch<T>::update_p_defer_pc_dist(cg->n, v.x, p, pn, v.P, v.r, v.m, v.st, slot, v.ws,
-                                               npr, s, par3, far);
-    if (defer && pc)
-      return Launch<T>::update_p_defer_pc(cg->n, v.x, p, pn, v.P, v.r, v.m, v.st, slot, v.ws, npr,
-                                          s, par3, cg->minv_nt);
     if (defer)
       return Launch<T>::update_p_defer(cg->n, v.x, p, pn, v.P, v.r, v.st, slot, v.ws, np_rr, s,
-                                       par3, far);
-    if (pc_dist)
-      return Launch<T>::update_xp_pc_dist(cg->n, v.x, p, v.r, v.m, v.st, slot, v.ws, npr, s, par3,
-                                          far);
-    if (pc)
-      return Launch<T>::update_xp_pc(cg->n, v.x, p, v.r, v.m, v.st, slot, v.ws, npr, s, par3,
-                                     cg->minv_nt);
-    return Launch<T>::update_xp(cg->n, v.x, p, v.r, v.st, slot, v.ws, np_rr, s, par3, far);
+                                       par3, vs);
+    return Launch<T>::update_xp(cg->n, v.x, p, v.r, v.st, slot, v.ws, np_rr, s, par3, vs);
   });
 }
 
@@ -3828,8 +3808,7 @@ extern "C" int cgx_cg_begin(cgx_cg *cg, const void *b, void *x, double tol,
       hipError_t e = Launch<T>::cg_init(A->dev, (const T *)xe, (const T *)b, v.r, v.P[0], v.st,
                                         v.ws, (T)tol, cap, s);
       if (e == hipSuccess && cg->precond)
-        e = (A->dist ? Launch<T>::pc_init_dist : Launch<T>::pc_init)(cg->n, v.r, v.m, v.P[0],
-                                                                     v.st, v.ws, s);
+        e = Launch<T>::pc_init(cg->n, v.r, v.m, v.P[0], v.st, v.ws, s, A->dist);
       if constexpr (std::is_same_v<T, double>) {  // block-Jacobi: p = z = M^-1 r, rz[0] = r.z
         if (e == hipSuccess && cg->blk_kind != CGX_BLOCK_NONE)
           e = blk_init(cg->n, cg->blk_bs, v.r, (const double *)cg->blk_w, v.P[0], v.st, v.ws, s);

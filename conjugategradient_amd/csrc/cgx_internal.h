@@ -203,6 +203,28 @@ struct SellSlice {
 
 struct PeerDev;  // cgx_objects.h
 
+// The vector step of a three-kernel body (update_r, then update_xp or
+// update_p_defer): which z the body uses and where the world value of its
+// dots comes from (the Z and kDots policies of cgx_kernels.hip). Built once
+// per body (cgx_abi.cpp enqueue_iter); the default is the plain single-device
+// body.
+template <typename T> struct VecStep {
+  // z = r when both are null; m: z = m o r, m = M^-1's diagonal (DESIGN.md
+  // §5b; m_nt: m through non-temporal loads on one device, an A/B switch of
+  // tools/pcg_bench.py); z: the buffer where blk_update_r left z = M^-1 r for
+  // the p update (block-Jacobi, DESIGN.md §5f: f64, one device)
+  const T *m = nullptr;
+  bool m_nt = false;
+  const T *z = nullptr;
+  // the dots: this device's partials (the np argument of each launcher); peer:
+  // a partitioned run's partials all-reduced inside the kernels (the device
+  // peer transport's fused form); ring: the world values read from the scalar
+  // ring (pAp[slot], rr[slot] or rrz[2 slot..]), where a separate all-reduce
+  // step put them
+  const PeerDev *peer = nullptr;
+  bool ring = false;
+};
+
 // ---- launchers (cgx_kernels.hip) --------------------------------------------
 struct CsrDev {
   int64_t n, nnz;
@@ -335,12 +357,13 @@ template <typename T> struct Launch {
                                      CgScalars<T> *st, RedWs<T> *ws, hipStream_t s);
   // the lean stencil walk's resident workgroups (its grid's upper bound)
   static int lean_resident();
-  // np_pap > 0: p.Ap from the spmv_dot partials; 0: from st->pAp[slot]
+  // np_pap: the spmv_dot partials p.Ap is summed from (plain body: 0 reads
+  // st->pAp[slot]). fused, rin and rule are the plain single-device body's.
   static hipError_t update_r(int64_t n, T *r, const T *Ap, CgScalars<T> *st, int slot,
                              RedWs<T> *ws, hipStream_t s, bool fused = false, int np_pap = 0,
                              int rev = 0, const T *rin = nullptr,  // rin: r_old (null: r)
                              int rule = 0,   // mode 4: the stop rule runs here
-                             const PeerDev *peer = nullptr);  // p.Ap all-reduced here
+                             const VecStep<T> &vs = {});
   // mode 4 (fused deferred-x iteration, cgx_abi.cpp enqueue_iter_fdefer):
   // kernel 1 computes p_k = r + beta p_{k-1} into pc where the SpMV reads it
   static bool fd_supported(const CsrDev &A);
@@ -428,16 +451,15 @@ template <typename T> struct Launch {
                                CgScalars<T> *st, int slot, RedWs<T> *ws, hipStream_t s);
   static hipError_t flush_x(int64_t n, T *x, const T *p, CgScalars<T> *st, int slot,
                             RedWs<T> *ws, hipStream_t s);
-  // np_rr > 0: r.r from the update_r partials; 0: from st->rr[slot]
-  // peer: a partitioned run's r.r all-reduced in the kernel (device peer
-  // transport; np_rr the local partials)
+  // np_rr: update_r's partials of r.r (and r.z) (plain body: 0 reads
+  // st->rr[slot])
   static hipError_t update_xp(int64_t n, T *x, T *p, const T *r, CgScalars<T> *st,
                               int slot, RedWs<T> *ws, int np_rr, hipStream_t s, int rev = 0,
-                              const PeerDev *peer = nullptr);
+                              const VecStep<T> &vs = {});
   static hipError_t update_p_defer(int64_t n, T *x, const T *p, T *pn, T *const P[4],
                                    const T *r, CgScalars<T> *st, int slot, RedWs<T> *ws,
                                    int np_rr, hipStream_t s, int rev = 0,
-                                   const PeerDev *peer = nullptr);
+                                   const VecStep<T> &vs = {});
   static hipError_t flush_defer(int64_t n, T *x, T *const P[4], CgScalars<T> *st,
                                 hipStream_t s);
   // batched CG (f64, one device, the mode-1 body): `width`
@@ -458,37 +480,11 @@ template <typename T> struct Launch {
   static hipError_t batch_update_xp(int64_t n, int width, T *X, int64_t ldx, T *p, const T *r,
                                     CgScalars<T> *st, int slot, BatchWs *ws, int np_rr,
                                     hipStream_t s);
-  // diagonal preconditioning (modes 1 and 3 on one device): the
-  // three vector kernels with z = m o r formed where r is in registers; m_nt:
-  // m read with non-temporal loads (an A/B switch, tools/pcg_bench.py)
+  // diagonal preconditioning, after cg_init: p = m o r, rz[0] = r.(m o r).
+  // dist (a partitioned matrix, the rank's own rows): the local r.z's
+  // double-length pair goes to ws->rz_part[0..1] as well
   static hipError_t pc_init(int64_t n, const T *r, const T *m, T *p, CgScalars<T> *st,
-                            RedWs<T> *ws, hipStream_t s);
-  static hipError_t update_r_pc(int64_t n, T *r, const T *Ap, const T *m, CgScalars<T> *st,
-                                int slot, RedWs<T> *ws, hipStream_t s, int np_pap, int rev,
-                                bool m_nt);
-  static hipError_t update_xp_pc(int64_t n, T *x, T *p, const T *r, const T *m,
-                                 CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr,
-                                 hipStream_t s, int rev, bool m_nt);
-  static hipError_t update_p_defer_pc(int64_t n, T *x, const T *p, T *pn, T *const P[4],
-                                      const T *r, const T *m, CgScalars<T> *st, int slot,
-                                      RedWs<T> *ws, int np_rr, hipStream_t s, int rev, bool m_nt);
-  // the same kernels on a partitioned matrix (the rank's own rows). peer: the
-  // device peer transport's fused form, the world p.Ap and {r.r, r.z} summed
-  // inside the kernels (np_*: the local partials); nullptr: the world values
-  // read from the scalar ring (pAp[slot], rrz[2 slot..]), where a separate
-  // all-reduce step put them. m through plain loads.
-  static hipError_t pc_init_dist(int64_t n, const T *r, const T *m, T *p, CgScalars<T> *st,
-                                 RedWs<T> *ws, hipStream_t s);
-  static hipError_t update_r_pc_dist(int64_t n, T *r, const T *Ap, const T *m, CgScalars<T> *st,
-                                     int slot, RedWs<T> *ws, hipStream_t s, int np_pap, int rev,
-                                     const PeerDev *peer);
-  static hipError_t update_xp_pc_dist(int64_t n, T *x, T *p, const T *r, const T *m,
-                                      CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr,
-                                      hipStream_t s, int rev, const PeerDev *peer);
-  static hipError_t update_p_defer_pc_dist(int64_t n, T *x, const T *p, T *pn, T *const P[4],
-                                           const T *r, const T *m, CgScalars<T> *st, int slot,
-                                           RedWs<T> *ws, int np_rr, hipStream_t s, int rev,
-                                           const PeerDev *peer);
+                            RedWs<T> *ws, hipStream_t s, bool dist);
   // dst[0], dst[1] = the sums of part_a, part_b (one launch; k_finalize twice)
   static hipError_t finalize2(const T *part_a, const T *part_b, int np, T *dst, hipStream_t s);
   // out[i] = 1 / (sum of row i's entries with col == i); bad[0] counts the
@@ -569,18 +565,13 @@ hipError_t blk_check(int64_t n, int bs, const double *W, unsigned long long *bad
 // after cg_init: p = z = M^-1 r, rz[0] = r.z
 hipError_t blk_init(int64_t n, int bs, const double *r, const double *W, double *p,
                     CgScalars<double> *st, RedWs<double> *ws, hipStream_t s);
-// the three-kernel body's vector kernels (modes 1 and 3): update_r stores z
-// over Ap (apz) and leaves blk_update_parts(n, bs) partials of r.r and r.z;
-// the p updates read z there
+// the three-kernel body's update_r (modes 1 and 3): it stores z over Ap (apz)
+// and leaves blk_update_parts(n, bs) partials of r.r and r.z; the p updates
+// (Launch<double>::update_xp, update_p_defer) read z there (VecStep::z)
 int blk_update_parts(int64_t n, int bs);
 hipError_t blk_update_r(int64_t n, int bs, double *r, double *apz, const double *W,
                         CgScalars<double> *st, int slot, RedWs<double> *ws, hipStream_t s,
                         int np_pap, int rev);
-hipError_t blk_update_xp(int64_t n, double *x, double *p, const double *z, CgScalars<double> *st,
-                         int slot, RedWs<double> *ws, int np_rr, hipStream_t s, int rev);
-hipError_t blk_update_p_defer(int64_t n, double *x, const double *p, double *pn,
-                              double *const P[4], const double *z, CgScalars<double> *st,
-                              int slot, RedWs<double> *ws, int np_rr, hipStream_t s, int rev);
 
 // value-code templates (cgx_abi.cpp build_value_templates): per slice the
 // hash of its 4-bit code chunk (0: wider than one chunk); the template slice

@@ -4383,21 +4383,144 @@ __device__ __forceinline__ void flush_group_range(int64_t n, T *__restrict__ x,
 }
 
 
-template <typename T, bool FUSED, bool PEER, bool SNT, bool GF = false, int KP = kPartsPerThread>
+// ---------------------------------------------------------------------------
+// The three vector bodies of the three-kernel iteration (update_r, update_xp,
+// update_p_defer) are each written once, typed on two policies: where z comes
+// from, and where the world value of the body's dot(s) comes from. With
+// z = r (ZPlain) only r.r exists, alpha = r.r / p.Ap and beta = r.r' / r.r;
+// a preconditioned body (Z::pc) has alpha = rz / p.Ap and
+// beta = rz' / rz with rz = r.z, while rxr stays the true r.r and the stop
+// rule is the plain one. r.z is accumulated and summed exactly as r.r is and
+// every other statement is shared, so with m == 1 (or W == I) every value is
+// the plain solver's, bit for bit.
+// ---------------------------------------------------------------------------
+// z is r: no m, no rz[]
+struct ZPlain {
+  static constexpr bool pc = false, diag = false, stored = false;
+  template <typename T, typename V> static __device__ __forceinline__ V ldm(const V *) {
+    return V{};
+  }
+  template <typename T> static __device__ __forceinline__ T z(T, T r) { return r; }
+};
+// z = m o r (m = M^-1's diagonal), never stored: z_i = m_i * r_i, rounded, is
+// formed where r_i is in a register, in update_r's second dot and in the p
+// update, the same expression in both.
+// MNT: m through non-temporal loads. m is read by update_r and again by the
+// p update and never written, so the default is plain loads, which let it
+// stay in L2 / the Infinity Cache between the two (A/B: tools/pcg_bench.py).
+template <bool MNT> struct ZDiag {
+  static constexpr bool pc = true, diag = true, stored = false;
+  template <typename T, typename V> static __device__ __forceinline__ V ldm(const V *m) {
+    return ldv<MNT, T>(m);
+  }
+  template <typename T> static __device__ __forceinline__ T z(T m, T r) { return m * r; }
+};
+// z = M^-1 r read from the buffer where k_update_r_blk left it (over Ap), in
+// r's place: the p updates touch neither r nor W (f64 only)
+struct ZStored {
+  static constexpr bool pc = true, diag = false, stored = true;
+  template <typename T, typename V> static __device__ __forceinline__ V ldm(const V *) {
+    return V{};
+  }
+  template <typename T> static __device__ __forceinline__ T z(T, T zv) { return zv; }
+};
+// The world value of a body's dots: this device's partials (the plain bodies
+// decide at run time between the partials, np > 0, and the scalar ring); the
+// partials all-reduced inside the kernel (the device peer transport's fused
+// form); or the scalar ring (st->pAp[slot], st->rrz[2 slot..]), where a
+// separate all-reduce step put them (host, RCCL, the peer one-waiter form).
+enum { kDotsLocal = 0, kDotsPeer = 1, kDotsRing = 2 };
+
+// "stop if a peer faulted, else world-sum or raise the fault": one dot of a
+// partitioned body all-reduced in the kernel that consumes it, under tag
+// base + tag (1: p.Ap in update_r, 2: r.r in the p update) instead of by a
+// k_peer_allreduce launch before the kernel. false: the body stops.
+template <typename T>
+__device__ __forceinline__ bool peer_world(Dd<T> d, int tag, CgScalars<T> *st, int slot,
+                                           const PeerDev *P, T *out) {
+  __shared__ double wres;
+  __shared__ int wok;
+  if (P->state->fault) {  // an earlier spin timed out: stop this body too
+    peer_fault(st, slot, P);
+    return false;
+  }
+  if (!peerdev::world_sum(Dd<double>((double)d.hi, (double)d.lo), P->state->arb[slot & 1] + tag,
+                          *P, &wres, &wok)) {
+    peer_fault(st, slot, P);
+    return false;
+  }
+  *out = (T)wres;
+  return true;
+}
+// the two-value form: a preconditioned body's {r.r, r.z}, this rank's two
+// double-length sums all-reduced together under tag base + 2
+// (peerdev::world_sum2)
+template <typename T>
+__device__ __forceinline__ bool peer_world2(Dd<T> rd, Dd<T> zd, CgScalars<T> *st, int slot,
+                                            const PeerDev *P, T *rr, T *rzn) {
+  __shared__ double wres2[2];
+  __shared__ int wok2;
+  if (P->state->fault) {  // an earlier spin timed out: stop this body too
+    peer_fault(st, slot, P);
+    return false;
+  }
+  if (!peerdev::world_sum2(Dd<double>((double)rd.hi, (double)rd.lo),
+                           Dd<double>((double)zd.hi, (double)zd.lo),
+                           P->state->arb[slot & 1] + 2, *P, wres2, &wok2)) {
+    peer_fault(st, slot, P);
+    return false;
+  }
+  *rr = (T)wres2[0];
+  *rzn = (T)wres2[1];
+  return true;
+}
+// the next body's tag base (workgroup 0, thread 0, after the stop rule)
+__device__ __forceinline__ void peer_next_base(int slot, const PeerDev *P) {
+  const unsigned long long t = P->state->arb[slot & 1] + 2;
+  P->state->ar = t;
+  P->state->arb[(slot + 1) & 1] = t;
+}
+
+// The stop rule (CG.hpp:396-404, 410-417, 436) on rxr, the r.r body `slot`
+// started with, by the one thread that writes the body's records: the body
+// count, whether the next body runs, and the stop code. records(nxt) stores
+// what the caller hands to the next body (rxr[nxt], rz[nxt], ..) between
+// active[nxt] and stopped.
+template <typename T, typename F>
+__device__ __forceinline__ void stop_rule(CgScalars<T> *st, int slot, T rxr, F records) {
+  const int nxt = (slot + 1) & 3;
+  const long long m = st->bodies + 1;
+  st->bodies = m;
+  const bool cond = isnan(rxr) || sqrt(rxr) <= st->tol;
+  const bool cont = !cond && m < st->cap;
+  st->active[nxt] = cont ? 1 : 0;
+  records(nxt);
+  st->stopped = cond ? 1 : (cont ? 0 : 2);
+}
+
+// r = r - alpha Ap; r.r, and with Z::pc r.z, in one sweep.
 // rin == r: in place (modes 1, 2); else r ping-pongs between two buffers.
+// SRC: kDotsPeer p.Ap from this rank's partials, then all-reduced here (tag
+// base + 1); kDotsRing the world p.Ap read from st->pAp[slot] (np_pap unused).
+// FUSED, GF and rule belong to the plain policy.
 // GF (mode 4, slot 3): after r, the group's deferred x updates (xf), also
 // when the body itself is inactive (the group's earlier bodies that ran).
+template <typename T, typename Z, int SRC, bool FUSED, bool SNT, bool GF = false,
+          int KP = kPartsPerThread>
 __device__ __forceinline__ void update_r_body(int64_t n, const T *rin, T *r,
-                                              const T *__restrict__ Ap, CgScalars<T> *st,
-                                              int slot, RedWs<T> *ws, int np_pap, int rev,
-                                              int rule, const PeerDev *P,
+                                              const T *__restrict__ Ap, const T *__restrict__ m,
+                                              CgScalars<T> *st, int slot, RedWs<T> *ws,
+                                              int np_pap, int rev, int rule, const PeerDev *P,
                                               const XFlush<T> *xf = nullptr) {
+  static_assert(!Z::stored && !(Z::pc && (FUSED || GF)), "no such update_r");
+  constexpr bool PEER = SRC == kDotsPeer;
   // rule (mode 4, kernel 2 of 2): this kernel also runs the stop rule
   // (CG.hpp:396-404, 436: on the r.r the body started with, which k_spmv_fd
   // recorded) and marks the body's x update pending (ran[slot])
   const auto *cst = (const __attribute__((address_space(4))) CgScalars<T> *)st;
   const bool act = cst->active[slot] != 0;  // branched on after the first loads
   __shared__ T red[8];
+  [[maybe_unused]] __shared__ T redz[8];
   __shared__ int flag;
   using V = typename Vec2<T>::V;
   const int64_t n2 = n >> 1;
@@ -4405,6 +4528,10 @@ __device__ __forceinline__ void update_r_body(int64_t n, const T *rin, T *r,
   V *r2 = reinterpret_cast<V *>(r);
   const V *ri2 = reinterpret_cast<const V *>(rin);
   const V *a2 = reinterpret_cast<const V *>(Ap);
+  const V *m2 = reinterpret_cast<const V *>(m);
+  // the clamped first loads of n = 1 reach one element past the end: r and Ap
+  // carry a slack element, a caller's m need not, so they read r instead
+  const V *m2f = n2 > 0 ? m2 : reinterpret_cast<const V *>(r);
   auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
   int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   // p.Ap: the spmv_dot partials (single device) or st (fused mode, or
@@ -4413,17 +4540,21 @@ __device__ __forceinline__ void update_r_body(int64_t n, const T *rin, T *r,
   // alpha), then the partials are summed while that block is in flight.
   // scalar loads (lgkmcnt): a vector load issued after the prefetch would
   // make its wait drain the prefetch too
-  const T rxr = cst->rxr[slot];
-  const T pAp_st = cst->pAp[slot];
+  // alpha's numerator: r.z, or the r.r the body started with (the rule's too)
+  const T num = Z::pc ? cst->rz[slot] : cst->rxr[slot];
+  constexpr bool ring_read = !Z::pc || SRC == kDotsRing;
+  T pAp_st = T(0);
+  if constexpr (ring_read) pAp_st = cst->pAp[slot];
   Dd<T> pl[KP];
-  const bool from_parts = !FUSED && np_pap > 0;
+  const bool from_parts = Z::pc ? SRC != kDotsRing : !FUSED && np_pap > 0;
   if (from_parts) parts_load(ws->pap_part, np_pap, pl);
-  V rv[kUR], av[kUR];
+  V rv[kUR], av[kUR], mv[kUR];
 #pragma unroll
   for (int u = 0; u < kUR; ++u) {  // clamped (r and Ap have a slack element): no branch
     const int64_t j = E(min(i + u * stride, n2 > 0 ? n2 - 1 : 0));
     rv[u] = ri2[j];
     av[u] = ldv<SNT, T>(a2 + j);  // Ap is dead after this kernel
+    mv[u] = Z::template ldm<T>(m2f + j);
   }
   // the group flush's alphas and flags of the earlier slots (written by
   // earlier launches; this one writes only slot 3's)
@@ -4437,11 +4568,12 @@ __device__ __forceinline__ void update_r_body(int64_t n, const T *rin, T *r,
     }
   }
   if (!act) {
-    keep(rxr);
-    keep(pAp_st);
+    keep(num);
+    if constexpr (ring_read) keep(pAp_st);
     if (from_parts) keep(pl);
     keep(rv);
     keep(av);
+    if constexpr (Z::diag) keep(mv);
     if ((FUSED || rule) && blockIdx.x == 0 && threadIdx.x == 0) st->active[(slot + 1) & 3] = 0;
     if constexpr (GF) {
       if (guse[0] || guse[1] || guse[2])
@@ -4450,45 +4582,31 @@ __device__ __forceinline__ void update_r_body(int64_t n, const T *rin, T *r,
     return;
   }
   const Dd<T> pd = from_parts ? parts_sum_dd(pl, np_pap, red) : Dd<T>(pAp_st);
-  T pAp = pd.value();
+  // (a preconditioned body takes the ring's value as it is)
+  T pAp = Z::pc && SRC == kDotsRing ? pAp_st : pd.value();
   // (PEER without partials: the one-waiter form's k_peer_allreduce has put
   // the world p.Ap into st already)
   if (PEER && from_parts) {
-    __shared__ double wres;
-    __shared__ int wok;
-    if (P->state->fault) {  // an earlier spin timed out: stop this body too
-      peer_fault(st, slot, P);
-      return;
-    }
-    if (!peerdev::world_sum(Dd<double>((double)pd.hi, (double)pd.lo),
-                            P->state->arb[slot & 1] + 1, *P, &wres, &wok)) {
-      peer_fault(st, slot, P);
-      return;
-    }
-    pAp = (T)wres;
+    if (!peer_world(pd, 1, st, slot, P, &pAp)) return;
   }
-  const T alpha = rxr / pAp;
+  const T alpha = num / pAp;
   if (!FUSED && blockIdx.x == 0 && threadIdx.x == 0) {  // the record; the deferred x update
     st->pAp[slot] = pAp;
     st->alpha[slot] = alpha;
     st->skip[slot] = 0;
-    if (rule) {  // stop rule, as k_update_xp
-      const long long m = st->bodies + 1;
-      st->bodies = m;
-      const bool cond = isnan(rxr) || sqrt(rxr) <= st->tol;
-      const bool cont = !cond && m < st->cap;
-      st->active[(slot + 1) & 3] = cont ? 1 : 0;
-      st->stopped = cond ? 1 : (cont ? 0 : 2);
+    if (rule) {
+      stop_rule(st, slot, num, [](int) {});
       st->ran[slot] = 1;
     }
   }
-  Dd<T> acc(T(0));  // r.r (double-length)
+  Dd<T> acc(T(0)), accz(T(0));  // r.r and r.z (double-length)
   for (bool first = true; i + (kUR - 1) * stride < n2; i += kUR * stride, first = false) {
     if (!first) {
 #pragma unroll
       for (int u = 0; u < kUR; ++u) {
         rv[u] = ri2[E(i + u * stride)];
         av[u] = ldv<SNT, T>(a2 + E(i + u * stride));
+        mv[u] = Z::template ldm<T>(m2 + E(i + u * stride));
       }
     }
 #pragma unroll
@@ -4498,21 +4616,32 @@ __device__ __forceinline__ void update_r_body(int64_t n, const T *rin, T *r,
       r2[E(i + u * stride)] = rv[u];
       acc += rv[u].x * rv[u].x;
       acc += rv[u].y * rv[u].y;
+      if constexpr (Z::pc) {
+        accz += rv[u].x * Z::z(mv[u].x, rv[u].x);
+        accz += rv[u].y * Z::z(mv[u].y, rv[u].y);
+      }
     }
   }
   for (; i < n2; i += stride) {
     V rv = ri2[E(i)];
     const V av = a2[E(i)];
+    V mv{};
+    if constexpr (Z::diag) mv = m2[E(i)];
     rv.x = rv.x - alpha * av.x;
     rv.y = rv.y - alpha * av.y;
     r2[E(i)] = rv;
     acc += rv.x * rv.x;
     acc += rv.y * rv.y;
+    if constexpr (Z::pc) {
+      accz += rv.x * Z::z(mv.x, rv.x);
+      accz += rv.y * Z::z(mv.y, rv.y);
+    }
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
     const T v = rin[n - 1] - alpha * Ap[n - 1];
     r[n - 1] = v;
     acc += v * v;
+    if constexpr (Z::diag) accz += v * Z::z(m[n - 1], v);
   }
   if constexpr (GF) {
     ga[3] = alpha;
@@ -4520,8 +4649,9 @@ __device__ __forceinline__ void update_r_body(int64_t n, const T *rin, T *r,
     flush_group_range<T>(n, xf->x, xf->P[0], xf->P[1], xf->P[2], xf->P[3], ga, guse, rev);
   }
   Dd<T> v = acc;
-  if constexpr (!FUSED) {  // this workgroup's share of r.r; the next kernel sums them
+  if constexpr (!FUSED) {  // this workgroup's shares of the dots; the next kernel sums them
     v = block_sum_dd(v, red);
+    if constexpr (Z::pc) accz = block_sum_dd(accz, redz);
     if (threadIdx.x == 0) {
       if (PEER && rule) {  // ... or this kernel's last workgroup (k_update_r_peer_rule)
         store_sc1(&ws->rr_part[2 * blockIdx.x], v.hi);
@@ -4530,23 +4660,20 @@ __device__ __forceinline__ void update_r_body(int64_t n, const T *rin, T *r,
         ws->rr_part[2 * blockIdx.x] = v.hi;
         ws->rr_part[2 * blockIdx.x + 1] = v.lo;
       }
+      if constexpr (Z::pc) {
+        ws->rz_part[2 * blockIdx.x] = accz.hi;
+        ws->rz_part[2 * blockIdx.x + 1] = accz.lo;
+      }
     }
     return;
   }
   if (grid_reduce_dd(v, ws, red, &flag) && threadIdx.x == 0) {
     st->rr[slot] = v.value();
-    if (FUSED) {
-      const int nxt = (slot + 1) & 3;
-      const T rxr = st->rxr[slot];
-      const long long m = st->bodies + 1;
-      st->bodies = m;
-      const bool cond = isnan(rxr) || sqrt(rxr) <= st->tol;
-      const bool cont = !cond && m < st->cap;
-      st->active[nxt] = cont ? 1 : 0;
-      st->rxr[nxt] = st->rr[slot];
-      st->xpend[slot] = 1;
-      st->stopped = cond ? 1 : (cont ? 0 : 2);
-    }
+    if (FUSED)
+      stop_rule(st, slot, st->rxr[slot], [=](int nxt) {
+        st->rxr[nxt] = st->rr[slot];
+        st->xpend[slot] = 1;
+      });
   }
 }
 
@@ -4557,11 +4684,11 @@ __global__ __launch_bounds__(kBlock) void k_update_r(int64_t n, const T *rin, T 
                                                      RedWs<T> *ws, int np_pap, int rev,
                                                      int rule) {
   if (stream_nt<T>(n))
-    update_r_body<T, FUSED, false, true, false, KP>(n, rin, r, Ap, st, slot, ws, np_pap, rev,
-                                                    rule, nullptr);
+    update_r_body<T, ZPlain, kDotsLocal, FUSED, true, false, KP>(n, rin, r, Ap, nullptr, st, slot,
+        ws, np_pap, rev, rule, nullptr);
   else
-    update_r_body<T, FUSED, false, false, false, KP>(n, rin, r, Ap, st, slot, ws, np_pap, rev,
-                                                     rule, nullptr);
+    update_r_body<T, ZPlain, kDotsLocal, FUSED, false, false, KP>(n, rin, r, Ap, nullptr, st, slot,
+                                                                  ws, np_pap, rev, rule, nullptr);
 }
 // Mode 4, slot 3: update_r with the stop rule and the group's x flush in one
 // launch (a separate flush launch's values, bit for bit)
@@ -4572,11 +4699,11 @@ __global__ __launch_bounds__(kBlock) void k_update_r_flush(int64_t n, T *r,
                                                            RedWs<T> *ws, int np_pap, int rev,
                                                            XFlush<T> xf) {
   if (stream_nt<T>(n))
-    update_r_body<T, false, false, true, true, KP>(n, r, r, Ap, st, slot, ws, np_pap, rev, 1,
-                                                   nullptr, &xf);
+    update_r_body<T, ZPlain, kDotsLocal, false, true, true, KP>(n, r, r, Ap, nullptr, st, slot, ws,
+                                                                np_pap, rev, 1, nullptr, &xf);
   else
-    update_r_body<T, false, false, false, true, KP>(n, r, r, Ap, st, slot, ws, np_pap, rev, 1,
-                                                    nullptr, &xf);
+    update_r_body<T, ZPlain, kDotsLocal, false, false, true, KP>(n, r, r, Ap, nullptr, st, slot, ws,
+                                                                 np_pap, rev, 1, nullptr, &xf);
 }
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_update_r_peer(int64_t n, T *r,
@@ -4585,9 +4712,11 @@ __global__ __launch_bounds__(kBlock) void k_update_r_peer(int64_t n, T *r,
                                                           RedWs<T> *ws, int np_pap, int rev,
                                                           PeerDev P) {
   if (stream_nt<T>(n))
-    update_r_body<T, false, true, true>(n, r, r, Ap, st, slot, ws, np_pap, rev, 0, &P);
+    update_r_body<T, ZPlain, kDotsPeer, false, true>(n, r, r, Ap, nullptr, st, slot, ws, np_pap,
+        rev, 0, &P);
   else
-    update_r_body<T, false, true, false>(n, r, r, Ap, st, slot, ws, np_pap, rev, 0, &P);
+    update_r_body<T, ZPlain, kDotsPeer, false, false>(n, r, r, Ap, nullptr, st, slot, ws, np_pap,
+        rev, 0, &P);
 }
 // true in the workgroup of the grid that arrives last (two-level tickets as
 // grid_reduce: ticket[b % kRedGroups], then top; each reset by its last
@@ -4626,9 +4755,11 @@ __global__ __launch_bounds__(kBlock) void k_update_r_peer_rule(int64_t n, T *r,
                                                                RedWs<T> *ws, int np_pap, int rev,
                                                                PeerDev P, XFlush<T> xf) {
   if (stream_nt<T>(n))
-    update_r_body<T, false, true, true, GF>(n, r, r, Ap, st, slot, ws, np_pap, rev, 1, &P, &xf);
+    update_r_body<T, ZPlain, kDotsPeer, false, true, GF>(n, r, r, Ap, nullptr, st, slot, ws, np_pap,
+                                                         rev, 1, &P, &xf);
   else
-    update_r_body<T, false, true, false, GF>(n, r, r, Ap, st, slot, ws, np_pap, rev, 1, &P, &xf);
+    update_r_body<T, ZPlain, kDotsPeer, false, false, GF>(n, r, r, Ap, nullptr, st, slot, ws,
+        np_pap, rev, 1, &P, &xf);
   // every workgroup arrives, whichever way it left the body (a ticket left
   // short would break the next grid reduction on this workspace)
   __shared__ int lastf;
@@ -4667,59 +4798,69 @@ __global__ __launch_bounds__(kBlock) void k_update_r_peer_rule(int64_t n, T *r,
   }
 }
 
-// x = x + alpha p ; p = r + beta p ; stop rule   (CG.hpp:390, 396-418, 436)
-template <typename T, bool PEER>
+// x = x + alpha p ; p = z + beta p ; stop rule   (CG.hpp:390, 396-418, 436)
+// r: the vector z is formed from (ZStored: the z buffer itself).
+// SRC: kDotsPeer the world r.r (with Z::pc {r.r, r.z}) all-reduced here (tag
+// base + 2); kDotsRing read from the scalar ring (preconditioned: st->rrz).
+template <typename T, typename Z, int SRC>
 __device__ __forceinline__ void update_xp_body(int64_t n, T *__restrict__ x, T *__restrict__ p,
-                                               const T *__restrict__ r, CgScalars<T> *st,
-                                               int slot, RedWs<T> *ws, int np_rr, int rev,
-                                               const PeerDev *P) {
+                                               const T *__restrict__ r, const T *__restrict__ m,
+                                               CgScalars<T> *st, int slot, RedWs<T> *ws,
+                                               int np_rr, int rev, const PeerDev *P) {
   const int nxt = (slot + 1) & 3;
   if (!st->active[slot]) {
     if (blockIdx.x == 0 && threadIdx.x == 0) st->active[nxt] = 0;
     return;
   }
   __shared__ T red[8];
+  [[maybe_unused]] __shared__ T redz[8];
   const T rxr = st->rxr[slot];
-  const T alpha = rxr / st->pAp[slot];
-  const Dd<T> rd = np_rr > 0 ? sum_parts_dd(ws->rr_part, np_rr, red) : Dd<T>(st->rr[slot]);
-  T rr = rd.value();
-  if constexpr (PEER) {  // r.r all-reduced here (tag base + 2)
-    __shared__ double wres;
-    __shared__ int wok;
-    if (P->state->fault) {  // an earlier spin timed out: stop this body too
-      peer_fault(st, slot, P);
-      return;
+  const T den = Z::pc ? st->rz[slot] : rxr;  // beta's denominator, alpha's numerator
+  const T alpha = den / st->pAp[slot];
+  T rr, rzn = T(0);
+  if constexpr (!Z::pc) {
+    const Dd<T> rd = np_rr > 0 ? sum_parts_dd(ws->rr_part, np_rr, red) : Dd<T>(st->rr[slot]);
+    rr = rd.value();
+    if constexpr (SRC == kDotsPeer) {
+      if (!peer_world(rd, 2, st, slot, P, &rr)) return;
     }
-    if (!peerdev::world_sum(Dd<double>((double)rd.hi, (double)rd.lo), P->state->arb[slot & 1] + 2, *P, &wres,
-                            &wok)) {
-      peer_fault(st, slot, P);
-      return;
+  } else if constexpr (SRC == kDotsRing) {
+    rr = st->rrz[2 * slot];
+    rzn = st->rrz[2 * slot + 1];
+  } else {
+    const Dd<T> rd = sum_parts_dd(ws->rr_part, np_rr, red);
+    rr = rd.value();
+    const Dd<T> zd = sum_parts_dd(ws->rz_part, np_rr, redz);
+    rzn = zd.value();
+    if constexpr (SRC == kDotsPeer) {
+      if (!peer_world2(rd, zd, st, slot, P, &rr, &rzn)) return;
     }
-    rr = (T)wres;
   }
-  const T beta = rr / rxr;
+  const T beta = (Z::pc ? rzn : rr) / den;
   using V = typename Vec2<T>::V;
   const int64_t n2 = n >> 1;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   V *x2 = reinterpret_cast<V *>(x);
   V *p2 = reinterpret_cast<V *>(p);
   const V *rv2 = reinterpret_cast<const V *>(r);
+  const V *m2 = reinterpret_cast<const V *>(m);
   auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
   int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   for (; i + 3 * stride < n2; i += 4 * stride) {
-    V xv[4], pv[4], rv[4];
+    V xv[4], pv[4], rv[4], mv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       xv[u] = x2[E(i + u * stride)];
       pv[u] = p2[E(i + u * stride)];
       rv[u] = rv2[E(i + u * stride)];
+      mv[u] = Z::template ldm<T>(m2 + E(i + u * stride));
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       xv[u].x = xv[u].x + alpha * pv[u].x;
       xv[u].y = xv[u].y + alpha * pv[u].y;
-      pv[u].x = rv[u].x + beta * pv[u].x;
-      pv[u].y = rv[u].y + beta * pv[u].y;
+      pv[u].x = Z::z(mv[u].x, rv[u].x) + beta * pv[u].x;
+      pv[u].y = Z::z(mv[u].y, rv[u].y) + beta * pv[u].y;
       x2[E(i + u * stride)] = xv[u];
       p2[E(i + u * stride)] = pv[u];
     }
@@ -4727,10 +4868,11 @@ __device__ __forceinline__ void update_xp_body(int64_t n, T *__restrict__ x, T *
   for (; i < n2; i += stride) {
     V xv = x2[E(i)], pv = p2[E(i)];
     const V rv = rv2[E(i)];
+    const V mv = Z::template ldm<T>(m2 + E(i));
     xv.x = xv.x + alpha * pv.x;
     xv.y = xv.y + alpha * pv.y;
-    pv.x = rv.x + beta * pv.x;
-    pv.y = rv.y + beta * pv.y;
+    pv.x = Z::z(mv.x, rv.x) + beta * pv.x;
+    pv.y = Z::z(mv.y, rv.y) + beta * pv.y;
     x2[E(i)] = xv;
     p2[E(i)] = pv;
   }
@@ -4738,21 +4880,19 @@ __device__ __forceinline__ void update_xp_body(int64_t n, T *__restrict__ x, T *
     if (n & 1) {
       const T pv = p[n - 1];
       x[n - 1] = x[n - 1] + alpha * pv;
-      p[n - 1] = r[n - 1] + beta * pv;
+      if constexpr (Z::diag)
+        p[n - 1] = Z::z(m[n - 1], r[n - 1]) + beta * pv;
+      else
+        p[n - 1] = r[n - 1] + beta * pv;
     }
-    if (np_rr > 0) st->rr[slot] = rr;  // the record
-    const long long m = st->bodies + 1;
-    st->bodies = m;
-    const bool cond = isnan(rxr) || sqrt(rxr) <= st->tol;
-    const bool cont = !cond && m < st->cap;
-    st->active[nxt] = cont ? 1 : 0;
-    st->rxr[nxt] = rr;
-    st->stopped = cond ? 1 : (cont ? 0 : 2);
-    if constexpr (PEER) {  // the next body's tag base
-      const unsigned long long t = P->state->arb[slot & 1] + 2;
-      P->state->ar = t;
-      P->state->arb[(slot + 1) & 1] = t;
-    }
+    // the records: the plain body writes rr[slot] only when it summed the
+    // partials (else the ring holds it already); a preconditioned one always
+    if (Z::pc || np_rr > 0) st->rr[slot] = rr;
+    stop_rule(st, slot, rxr, [=](int) {
+      st->rxr[nxt] = rr;
+      if constexpr (Z::pc) st->rz[nxt] = rzn;
+    });
+    if constexpr (SRC == kDotsPeer) peer_next_base(slot, P);
   }
 }
 template <typename T>
@@ -4761,7 +4901,7 @@ __global__ __launch_bounds__(kBlock) void k_update_xp(int64_t n, T *__restrict__
                                                       const T *__restrict__ r,
                                                       CgScalars<T> *st, int slot,
                                                       RedWs<T> *ws, int np_rr, int rev) {
-  update_xp_body<T, false>(n, x, p, r, st, slot, ws, np_rr, rev, nullptr);
+  update_xp_body<T, ZPlain, kDotsLocal>(n, x, p, r, nullptr, st, slot, ws, np_rr, rev, nullptr);
 }
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_update_xp_peer(int64_t n, T *__restrict__ x,
@@ -4770,7 +4910,7 @@ __global__ __launch_bounds__(kBlock) void k_update_xp_peer(int64_t n, T *__restr
                                                            CgScalars<T> *st, int slot,
                                                            RedWs<T> *ws, int np_rr, int rev,
                                                            PeerDev P) {
-  update_xp_body<T, true>(n, x, p, r, st, slot, ws, np_rr, rev, &P);
+  update_xp_body<T, ZPlain, kDotsPeer>(n, x, p, r, nullptr, st, slot, ws, np_rr, rev, &P);
 }
 
 // Batched CG: k_update_r and k_update_xp over the interleaved
@@ -5315,66 +5455,102 @@ template <typename T> int Launch<T>::grid_elems(int64_t n, int cap) {
 // 8 N + 8 N (x) + 24 N (p0..p2) bytes once instead of 16 N four times.
 // In slot 3, pn is P0 (p_{k+1} replaces p_{k-3}): every element's flush
 // operands are loaded before its stores, and pn / P0 carry no __restrict__.
-template <typename T, bool FLUSH, bool PEER, bool SNT>
+// Z, SRC: as update_xp_body's (the alphas the flush applies are update_r's,
+// rz / p.Ap with Z::pc).
+template <typename T, typename Z, int SRC, bool FLUSH, bool SNT>
 __device__ __forceinline__ void update_p_defer_body(int64_t n, T *__restrict__ x, const T *p,
                                                     T *pn, const T *P0, const T *P1,
                                                     const T *P2, const T *__restrict__ r,
-                                                    CgScalars<T> *st, int slot, RedWs<T> *ws,
-                                                    int np_rr, int rev, const PeerDev *PD) {
+                                                    const T *__restrict__ m, CgScalars<T> *st,
+                                                    int slot, RedWs<T> *ws, int np_rr, int rev,
+                                                    const PeerDev *PD) {
   const int nxt = (slot + 1) & 3;
-  // the flag, rxr and the r.r partials in one round trip
+  // the flag, rxr (rz) and the dots' partials in one round trip
   const auto *cst = (const __attribute__((address_space(4))) CgScalars<T> *)st;
   const bool act = cst->active[slot] != 0;
   const T rxr = cst->rxr[slot];
-  const T rr_st = cst->rr[slot];
-  Dd<T> pl[kPartsPerThread];
-  if (np_rr > 0) parts_load_np(ws->rr_part, np_rr, pl);
+  const T den = Z::pc ? cst->rz[slot] : rxr;  // beta's denominator
+  // the dots from the ring (the plain body: when it has no partials)
+  constexpr bool ring_read = !Z::pc || SRC == kDotsRing;
+  const bool from_parts = Z::pc ? SRC != kDotsRing : np_rr > 0;
+  T rr_st = T(0), rz_st = T(0);
+  if constexpr (!Z::pc) {
+    rr_st = cst->rr[slot];
+  } else if constexpr (SRC == kDotsRing) {
+    rr_st = cst->rrz[2 * slot];
+    rz_st = cst->rrz[2 * slot + 1];
+  }
+  Dd<T> pl[kPartsPerThread], plz[kPartsPerThread];
+  if (from_parts) {
+    parts_load_np(ws->rr_part, np_rr, pl);
+    if constexpr (Z::pc) parts_load_np(ws->rz_part, np_rr, plz);
+  }
   using V = typename Vec2<T>::V;
   const int64_t n2 = n >> 1;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
   int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  // the non-flushing body: this thread's first four elements of p_k and r
+  const V *p2 = reinterpret_cast<const V *>(p);
+  const V *rv2 = reinterpret_cast<const V *>(r);
+  const V *m2 = reinterpret_cast<const V *>(m);
+  // the non-flushing body: this thread's first four elements of p_k, r and m
   // go out with the partials, before beta (as update_r's first block), so
-  // their round trip overlaps the partial sum
-  V pv0[4], rv0[4];
+  // their round trip overlaps the partial sum. Clamped, no branch: for n = 1
+  // they reach one element past the end, where r carries a slack element; a
+  // caller's m need not, so its load reads r, and with ZStored p's reads the
+  // z buffer (the Ap buffer, which carries one) at element 0.
+  V pv0[4], rv0[4], mv0[4];
   if constexpr (!FLUSH) {
+    const V *p2f = !Z::stored || n2 > 0 ? p2 : rv2;
+    const V *m2f = n2 > 0 ? m2 : rv2;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {  // clamped (p and r have a slack element): no branch
-      const int64_t j = E(min(i + u * stride, n2 > 0 ? n2 - 1 : 0));
-      pv0[u] = ldv<SNT, T>(reinterpret_cast<const V *>(p) + j);
-      rv0[u] = ldv<SNT, T>(reinterpret_cast<const V *>(r) + j);
+    for (int u = 0; u < 4; ++u) {
+      const int64_t j = Z::stored ? (n2 > 0 ? E(min(i + u * stride, n2 - 1)) : 0)
+                                  : E(min(i + u * stride, n2 > 0 ? n2 - 1 : 0));
+      pv0[u] = ldv<SNT, T>(p2f + j);
+      rv0[u] = ldv<SNT, T>(rv2 + j);
+      mv0[u] = Z::template ldm<T>(m2f + j);
     }
   }
   if (!act) {
     keep(rxr);
-    keep(rr_st);
-    if (np_rr > 0) keep(pl);
+    if constexpr (Z::pc) keep(den);
+    if constexpr (ring_read) keep(rr_st);
+    if constexpr (Z::pc && ring_read) keep(rz_st);
+    if (from_parts) {
+      keep(pl);
+      if constexpr (Z::pc) keep(plz);
+    }
     if constexpr (!FLUSH) {
       keep(pv0);
       keep(rv0);
+      if constexpr (Z::diag) keep(mv0);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) st->active[nxt] = 0;
     return;
   }
   __shared__ T red[8];
-  const Dd<T> rd = np_rr > 0 ? parts_sum_dd(pl, np_rr, red) : Dd<T>(rr_st);
-  T rr = rd.value();
-  if constexpr (PEER) {  // r.r all-reduced here (tag base + 2)
-    __shared__ double wres;
-    __shared__ int wok;
-    if (PD->state->fault) {  // an earlier spin timed out: stop this body too
-      peer_fault(st, slot, PD);
-      return;
+  [[maybe_unused]] __shared__ T redz[8];
+  T rr, rzn = T(0);
+  if constexpr (!Z::pc) {
+    const Dd<T> rd = from_parts ? parts_sum_dd(pl, np_rr, red) : Dd<T>(rr_st);
+    rr = rd.value();
+    if constexpr (SRC == kDotsPeer) {
+      if (!peer_world(rd, 2, st, slot, PD, &rr)) return;
     }
-    if (!peerdev::world_sum(Dd<double>((double)rd.hi, (double)rd.lo), PD->state->arb[slot & 1] + 2, *PD,
-                            &wres, &wok)) {
-      peer_fault(st, slot, PD);
-      return;
+  } else if constexpr (SRC == kDotsRing) {
+    rr = rr_st;
+    rzn = rz_st;
+  } else {
+    const Dd<T> rd = parts_sum_dd(pl, np_rr, red);
+    const Dd<T> zd = parts_sum_dd(plz, np_rr, redz);
+    rr = rd.value();
+    rzn = zd.value();
+    if constexpr (SRC == kDotsPeer) {
+      if (!peer_world2(rd, zd, st, slot, PD, &rr, &rzn)) return;
     }
-    rr = (T)wres;
   }
-  const T beta = rr / rxr;
+  const T beta = (Z::pc ? rzn : rr) / den;
   // slot-3 flush: alphas and skips of the group, written by earlier launches
   T a[4] = {T(0), T(0), T(0), T(0)};
   bool use[4] = {false, false, false, false};
@@ -5385,9 +5561,7 @@ __device__ __forceinline__ void update_p_defer_body(int64_t n, T *__restrict__ x
       use[t] = st->skip[t] == 0;
     }
   }
-  const V *p2 = reinterpret_cast<const V *>(p);
   V *pn2 = reinterpret_cast<V *>(pn);
-  const V *rv2 = reinterpret_cast<const V *>(r);
   V *x2 = reinterpret_cast<V *>(x);
   const V *Q[3] = {reinterpret_cast<const V *>(P0), reinterpret_cast<const V *>(P1),
                    reinterpret_cast<const V *>(P2)};
@@ -5399,6 +5573,7 @@ __device__ __forceinline__ void update_p_defer_body(int64_t n, T *__restrict__ x
     // profiles/r02_pupd_nt.log)
     const V pv = ldv<SNT, T>(p2 + i);
     const V rv = ldv<SNT, T>(rv2 + i);
+    const V mv = Z::template ldm<T>(m2 + i);
     V q[3], xv;
     if constexpr (FLUSH) {  // x and the old p buffers: not read again soon
       xv = ldv<SNT, T>(x2 + i);
@@ -5406,8 +5581,8 @@ __device__ __forceinline__ void update_p_defer_body(int64_t n, T *__restrict__ x
       for (int t = 0; t < 3; ++t) q[t] = ldv<SNT, T>(Q[t] + i);  // before pn (= P0) is written
     }
     V o;
-    o.x = rv.x + beta * pv.x;
-    o.y = rv.y + beta * pv.y;
+    o.x = Z::z(mv.x, rv.x) + beta * pv.x;
+    o.y = Z::z(mv.y, rv.y) + beta * pv.y;
     if constexpr (FLUSH) {
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
@@ -5431,8 +5606,8 @@ __device__ __forceinline__ void update_p_defer_body(int64_t n, T *__restrict__ x
     for (int u = 0; u < 4; ++u) {
       if (i + u * stride < n2) {
         V o;
-        o.x = rv0[u].x + beta * pv0[u].x;
-        o.y = rv0[u].y + beta * pv0[u].y;
+        o.x = Z::z(mv0[u].x, rv0[u].x) + beta * pv0[u].x;
+        o.y = Z::z(mv0[u].y, rv0[u].y) + beta * pv0[u].y;
         pn2[E(i + u * stride)] = o;
       }
     }
@@ -5453,27 +5628,23 @@ __device__ __forceinline__ void update_p_defer_body(int64_t n, T *__restrict__ x
           if (use[t]) xv = xv + a[t] * Ps[t][n - 1];
         x[n - 1] = xv;
       }
-      pn[n - 1] = r[n - 1] + beta * pv;
+      if constexpr (Z::diag)
+        pn[n - 1] = Z::z(m[n - 1], r[n - 1]) + beta * pv;
+      else
+        pn[n - 1] = r[n - 1] + beta * pv;
     }
-    // stop rule, as k_update_xp
-    if (np_rr > 0) st->rr[slot] = rr;  // the record
-    const long long m = st->bodies + 1;
-    st->bodies = m;
-    const bool cond = isnan(rxr) || sqrt(rxr) <= st->tol;
-    const bool cont = !cond && m < st->cap;
-    st->active[nxt] = cont ? 1 : 0;
-    st->rxr[nxt] = rr;
-    st->stopped = cond ? 1 : (cont ? 0 : 2);
+    // the records, as update_xp_body's
+    if (Z::pc || np_rr > 0) st->rr[slot] = rr;
+    stop_rule(st, slot, rxr, [=](int) {
+      st->rxr[nxt] = rr;
+      if constexpr (Z::pc) st->rz[nxt] = rzn;
+    });
     if constexpr (FLUSH) {
       for (int t = 0; t < 4; ++t) st->ran[t] = 0;
     } else {
       st->ran[slot] = 1;
     }
-    if constexpr (PEER) {  // the next body's tag base
-      const unsigned long long t = PD->state->arb[slot & 1] + 2;
-      PD->state->ar = t;
-      PD->state->arb[(slot + 1) & 1] = t;
-    }
+    if constexpr (SRC == kDotsPeer) peer_next_base(slot, PD);
   }
 }
 template <typename T, bool FLUSH>
@@ -5484,11 +5655,11 @@ __global__ __launch_bounds__(kBlock) void k_update_p_defer(int64_t n, T *__restr
                                                            CgScalars<T> *st, int slot,
                                                            RedWs<T> *ws, int np_rr, int rev) {
   if (stream_nt<T>(n))
-    update_p_defer_body<T, FLUSH, false, true>(n, x, p, pn, P0, P1, P2, r, st, slot, ws, np_rr,
-                                               rev, nullptr);
+    update_p_defer_body<T, ZPlain, kDotsLocal, FLUSH, true>(n, x, p, pn, P0, P1, P2, r, nullptr, st,
+        slot, ws, np_rr, rev, nullptr);
   else
-    update_p_defer_body<T, FLUSH, false, false>(n, x, p, pn, P0, P1, P2, r, st, slot, ws, np_rr,
-                                                rev, nullptr);
+    update_p_defer_body<T, ZPlain, kDotsLocal, FLUSH, false>(n, x, p, pn, P0, P1, P2, r, nullptr,
+        st, slot, ws, np_rr, rev, nullptr);
 }
 template <typename T, bool FLUSH>
 __global__ __launch_bounds__(kBlock) void k_update_p_defer_peer(
@@ -5496,11 +5667,11 @@ __global__ __launch_bounds__(kBlock) void k_update_p_defer_peer(
     const T *__restrict__ r, CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr, int rev,
     PeerDev PD) {
   if (stream_nt<T>(n))
-    update_p_defer_body<T, FLUSH, true, true>(n, x, p, pn, P0, P1, P2, r, st, slot, ws, np_rr,
-                                              rev, &PD);
+    update_p_defer_body<T, ZPlain, kDotsPeer, FLUSH, true>(n, x, p, pn, P0, P1, P2, r, nullptr, st,
+        slot, ws, np_rr, rev, &PD);
   else
-    update_p_defer_body<T, FLUSH, true, false>(n, x, p, pn, P0, P1, P2, r, st, slot, ws, np_rr,
-                                               rev, &PD);
+    update_p_defer_body<T, ZPlain, kDotsPeer, FLUSH, false>(n, x, p, pn, P0, P1, P2, r, nullptr, st,
+        slot, ws, np_rr, rev, &PD);
 }
 
 // End of a run in mode 3: apply the bodies of the current group that ran and
@@ -5561,12 +5732,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_lean_updr_rule_flush(
     st->pAp[slot] = pAp;
     st->alpha[slot] = alpha;
     st->skip[slot] = 0;
-    const long long m = st->bodies + 1;  // stop rule, as k_update_xp
-    st->bodies = m;
-    const bool cond = isnan(rxr) || sqrt(rxr) <= st->tol;
-    const bool cont = !cond && m < st->cap;
-    st->active[(slot + 1) & 3] = cont ? 1 : 0;
-    st->stopped = cond ? 1 : (cont ? 0 : 2);
+    stop_rule(st, slot, rxr, [](int) {});
     st->ran[slot] = 1;
   }
   const T *vd = static_cast<const T *>(A.svdict);
@@ -5596,45 +5762,21 @@ __global__ __launch_bounds__(kBlock) void k_spmv_lean_updr_rule_flush(
 // ---------------------------------------------------------------------------
 // Diagonal preconditioning (cgx_cg_set_precond): the vector
 // kernels of modes 1 and 3 on one device with z = m o r (m = M^-1's diagonal)
-// never stored: z_i = m_i * r_i, rounded, is formed where r_i is in a
-// register, in update_r's second dot and in the p update, the same
-// expression in both. alpha = rz / p.Ap and beta = rz' / rz with rz = r.z;
-// rxr stays the true r.r and the stop rule is the plain one. The kernels
-// mirror k_update_r, k_update_xp and k_update_p_defer statement for statement
-// (those are untouched), and r.z is accumulated and summed exactly as r.r is,
-// so with m == 1 every value is the plain solver's, bit for bit.
-// MNT: m through non-temporal loads. m is read by update_r and again by the
-// p update and never written, so the default is plain loads, which let it
-// stay in L2 / the Infinity Cache between the two (A/B: tools/pcg_bench.py).
+// never stored: the bodies of k_update_r, k_update_xp and k_update_p_defer
+// with the ZDiag policy. On a partitioned matrix (the rank's own rows) the
+// world p.Ap and {r.r, r.z} are all-reduced inside the kernels (_peer) or
+// read from the scalar ring (_ring), m through plain loads.
 // ---------------------------------------------------------------------------
 
-// after k_cg_init: p = m o r and rz[0] = r.(m o r) (single device)
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_pc_init(int64_t n, const T *__restrict__ r,
-                                                    const T *__restrict__ m, T *__restrict__ p,
-                                                    CgScalars<T> *st, RedWs<T> *ws) {
-  __shared__ T red[8];
-  __shared__ int flag;
-  Dd<T> acc(T(0));
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    const T rv = r[i];
-    const T z = m[i] * rv;
-    p[i] = z;
-    acc += rv * z;
-  }
-  if (grid_reduce_dd(acc, ws, red, &flag) && threadIdx.x == 0) st->rz[0] = acc.value();
-}
-
-// k_pc_init on a partitioned matrix (the rank's own rows): rz[0] is the
-// local value until the init all-reduce replaces it; its double-length pair
-// goes to rz_part[0..1] as well, where the peer transport's all-reduce takes
-// it (as k_cg_init leaves r.r's pair in rr_part[0..1])
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_pc_init_dist(int64_t n, const T *__restrict__ r,
-                                                         const T *__restrict__ m,
-                                                         T *__restrict__ p, CgScalars<T> *st,
-                                                         RedWs<T> *ws) {
+// after k_cg_init: p = m o r and rz[0] = r.(m o r).
+// DIST (a partitioned matrix, the rank's own rows): rz[0] is the local value
+// until the init all-reduce replaces it; its double-length pair goes to
+// rz_part[0..1] as well, where the peer transport's all-reduce takes it (as
+// k_cg_init leaves r.r's pair in rr_part[0..1])
+template <typename T, bool DIST>
+__device__ __forceinline__ void pc_init_body(int64_t n, const T *__restrict__ r,
+                                             const T *__restrict__ m, T *__restrict__ p,
+                                             CgScalars<T> *st, RedWs<T> *ws) {
   __shared__ T red[8];
   __shared__ int flag;
   Dd<T> acc(T(0));
@@ -5647,148 +5789,42 @@ __global__ __launch_bounds__(kBlock) void k_pc_init_dist(int64_t n, const T *__r
   }
   if (grid_reduce_dd(acc, ws, red, &flag) && threadIdx.x == 0) {
     st->rz[0] = acc.value();
-    ws->rz_part[0] = acc.hi;
-    ws->rz_part[1] = acc.lo;
+    if constexpr (DIST) {
+      ws->rz_part[0] = acc.hi;
+      ws->rz_part[1] = acc.lo;
+    }
   }
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_pc_init(int64_t n, const T *__restrict__ r,
+                                                    const T *__restrict__ m, T *__restrict__ p,
+                                                    CgScalars<T> *st, RedWs<T> *ws) {
+  pc_init_body<T, false>(n, r, m, p, st, ws);
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_pc_init_dist(int64_t n, const T *__restrict__ r,
+                                                         const T *__restrict__ m,
+                                                         T *__restrict__ p, CgScalars<T> *st,
+                                                         RedWs<T> *ws) {
+  pc_init_body<T, true>(n, r, m, p, st, ws);
 }
 
 // r = r - alpha Ap with alpha = rz / p.Ap; r.r and r.(m o r) in one sweep
-// (update_r_body's single-device, non-fused form)
-// D (partitioned matrices): 0 one device; 1 the device peer transport's fused
-// form, p.Ap all-reduced here (peerdev::world_sum, tag base + 1, as
-// update_r_body's PEER); 2 the world p.Ap read from st->pAp[slot], where a
-// separate all-reduce step put it (host, RCCL, the peer one-waiter form)
-template <typename T, bool SNT, bool MNT, int KP, int D = 0>
-__device__ __forceinline__ void update_r_pc_body(int64_t n, T *r, const T *__restrict__ Ap,
-                                                 const T *__restrict__ m, CgScalars<T> *st,
-                                                 int slot, RedWs<T> *ws, int np_pap, int rev,
-                                                 const PeerDev *P = nullptr) {
-  const auto *cst = (const __attribute__((address_space(4))) CgScalars<T> *)st;
-  const bool act = cst->active[slot] != 0;  // branched on after the first loads
-  __shared__ T red[8];
-  __shared__ T redz[8];
-  using V = typename Vec2<T>::V;
-  const int64_t n2 = n >> 1;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  V *r2 = reinterpret_cast<V *>(r);
-  const V *a2 = reinterpret_cast<const V *>(Ap);
-  const V *m2 = reinterpret_cast<const V *>(m);
-  // the clamped first loads of n = 1 reach one element past the end: r and Ap
-  // carry a slack element, a caller's m need not, so they read r instead
-  const V *m2f = n2 > 0 ? m2 : reinterpret_cast<const V *>(r);
-  auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
-  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const T rz = cst->rz[slot];
-  T pAp_st = T(0);
-  if constexpr (D == 2) pAp_st = cst->pAp[slot];
-  Dd<T> pl[KP];
-  if constexpr (D != 2) parts_load(ws->pap_part, np_pap, pl);
-  V rv[kUR], av[kUR], mv[kUR];
-#pragma unroll
-  for (int u = 0; u < kUR; ++u) {  // clamped: no branch
-    const int64_t j = E(min(i + u * stride, n2 > 0 ? n2 - 1 : 0));
-    rv[u] = r2[j];
-    av[u] = ldv<SNT, T>(a2 + j);  // Ap is dead after this kernel
-    mv[u] = ldv<MNT, T>(m2f + j);
-  }
-  if (!act) {
-    keep(rz);
-    if constexpr (D == 2) keep(pAp_st);
-    if constexpr (D != 2) keep(pl);
-    keep(rv);
-    keep(av);
-    keep(mv);
-    return;
-  }
-  T pAp;
-  if constexpr (D == 2) {
-    pAp = pAp_st;
-  } else {
-    const Dd<T> pd = parts_sum_dd(pl, np_pap, red);
-    pAp = pd.value();
-    if constexpr (D == 1) {
-      __shared__ double wres;
-      __shared__ int wok;
-      if (P->state->fault) {  // an earlier spin timed out: stop this body too
-        peer_fault(st, slot, P);
-        return;
-      }
-      if (!peerdev::world_sum(Dd<double>((double)pd.hi, (double)pd.lo),
-                              P->state->arb[slot & 1] + 1, *P, &wres, &wok)) {
-        peer_fault(st, slot, P);
-        return;
-      }
-      pAp = (T)wres;
-    }
-  }
-  const T alpha = rz / pAp;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {  // the record; the deferred x update
-    st->pAp[slot] = pAp;
-    st->alpha[slot] = alpha;
-    st->skip[slot] = 0;
-  }
-  Dd<T> acc(T(0)), accz(T(0));  // r.r and r.z (double-length)
-  for (bool first = true; i + (kUR - 1) * stride < n2; i += kUR * stride, first = false) {
-    if (!first) {
-#pragma unroll
-      for (int u = 0; u < kUR; ++u) {
-        rv[u] = r2[E(i + u * stride)];
-        av[u] = ldv<SNT, T>(a2 + E(i + u * stride));
-        mv[u] = ldv<MNT, T>(m2 + E(i + u * stride));
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kUR; ++u) {
-      rv[u].x = rv[u].x - alpha * av[u].x;
-      rv[u].y = rv[u].y - alpha * av[u].y;
-      r2[E(i + u * stride)] = rv[u];
-      acc += rv[u].x * rv[u].x;
-      acc += rv[u].y * rv[u].y;
-      accz += rv[u].x * (mv[u].x * rv[u].x);
-      accz += rv[u].y * (mv[u].y * rv[u].y);
-    }
-  }
-  for (; i < n2; i += stride) {
-    V rv = r2[E(i)];
-    const V av = a2[E(i)];
-    const V mv = m2[E(i)];
-    rv.x = rv.x - alpha * av.x;
-    rv.y = rv.y - alpha * av.y;
-    r2[E(i)] = rv;
-    acc += rv.x * rv.x;
-    acc += rv.y * rv.y;
-    accz += rv.x * (mv.x * rv.x);
-    accz += rv.y * (mv.y * rv.y);
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const T v = r[n - 1] - alpha * Ap[n - 1];
-    r[n - 1] = v;
-    acc += v * v;
-    accz += v * (m[n - 1] * v);
-  }
-  // this workgroup's shares of the two dots; the next kernel sums them
-  acc = block_sum_dd(acc, red);
-  accz = block_sum_dd(accz, redz);
-  if (threadIdx.x == 0) {
-    ws->rr_part[2 * blockIdx.x] = acc.hi;
-    ws->rr_part[2 * blockIdx.x + 1] = acc.lo;
-    ws->rz_part[2 * blockIdx.x] = accz.hi;
-    ws->rz_part[2 * blockIdx.x + 1] = accz.lo;
-  }
-}
 template <typename T, bool MNT, int KP>
 __global__ __launch_bounds__(kBlock) void k_update_r_pc(int64_t n, T *r, const T *__restrict__ Ap,
                                                         const T *__restrict__ m,
                                                         CgScalars<T> *st, int slot,
                                                         RedWs<T> *ws, int np_pap, int rev) {
   if (stream_nt<T>(n))
-    update_r_pc_body<T, true, MNT, KP>(n, r, Ap, m, st, slot, ws, np_pap, rev);
+    update_r_body<T, ZDiag<MNT>, kDotsLocal, false, true, false, KP>(n, r, r, Ap, m, st, slot, ws,
+                                                                     np_pap, rev, 0, nullptr);
   else
-    update_r_pc_body<T, false, MNT, KP>(n, r, Ap, m, st, slot, ws, np_pap, rev);
+    update_r_body<T, ZDiag<MNT>, kDotsLocal, false, false, false, KP>(n, r, r, Ap, m, st, slot, ws,
+                                                                      np_pap, rev, 0, nullptr);
 }
 
-// the partitioned forms (update_r_pc_body's D): the peer transport's fused
-// form, and the form behind a separate all-reduce step (np_pap unused)
+// the partitioned forms: the peer transport's fused form, and the form behind
+// a separate all-reduce step (np_pap unused)
 template <typename T, int KP>
 __global__ __launch_bounds__(kBlock) void k_update_r_pc_peer(int64_t n, T *r,
                                                              const T *__restrict__ Ap,
@@ -5797,9 +5833,11 @@ __global__ __launch_bounds__(kBlock) void k_update_r_pc_peer(int64_t n, T *r,
                                                              RedWs<T> *ws, int np_pap, int rev,
                                                              PeerDev P) {
   if (stream_nt<T>(n))
-    update_r_pc_body<T, true, false, KP, 1>(n, r, Ap, m, st, slot, ws, np_pap, rev, &P);
+    update_r_body<T, ZDiag<false>, kDotsPeer, false, true, false, KP>(n, r, r, Ap, m, st, slot, ws,
+                                                                      np_pap, rev, 0, &P);
   else
-    update_r_pc_body<T, false, false, KP, 1>(n, r, Ap, m, st, slot, ws, np_pap, rev, &P);
+    update_r_body<T, ZDiag<false>, kDotsPeer, false, false, false, KP>(n, r, r, Ap, m, st, slot, ws,
+                                                                       np_pap, rev, 0, &P);
 }
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_update_r_pc_ring(int64_t n, T *r,
@@ -5808,28 +5846,17 @@ __global__ __launch_bounds__(kBlock) void k_update_r_pc_ring(int64_t n, T *r,
                                                              CgScalars<T> *st, int slot,
                                                              RedWs<T> *ws, int rev) {
   if (stream_nt<T>(n))
-    update_r_pc_body<T, true, false, 4, 2>(n, r, Ap, m, st, slot, ws, 0, rev);
+    update_r_body<T, ZDiag<false>, kDotsRing, false, true, false, 4>(n, r, r, Ap, m, st, slot, ws,
+        0, rev, 0, nullptr);
   else
-    update_r_pc_body<T, false, false, 4, 2>(n, r, Ap, m, st, slot, ws, 0, rev);
+    update_r_body<T, ZDiag<false>, kDotsRing, false, false, false, 4>(n, r, r, Ap, m, st, slot, ws,
+        0, rev, 0, nullptr);
 }
 
-// the stop rule and the records of a preconditioned body (workgroup 0,
-// thread 0 of its p update), as k_update_xp's
-template <typename T>
-__device__ __forceinline__ void pc_stop_rule(CgScalars<T> *st, int slot, T rxr, T rr, T rzn) {
-  const int nxt = (slot + 1) & 3;
-  st->rr[slot] = rr;  // the record
-  const long long mb = st->bodies + 1;
-  st->bodies = mb;
-  const bool cond = isnan(rxr) || sqrt(rxr) <= st->tol;
-  const bool cont = !cond && mb < st->cap;
-  st->active[nxt] = cont ? 1 : 0;
-  st->rxr[nxt] = rr;
-  st->rz[nxt] = rzn;
-  st->stopped = cond ? 1 : (cont ? 0 : 2);
-}
-
-// mode 1: x = x + alpha p ; p = m o r + beta p ; stop rule (k_update_xp)
+// mode 1: x = x + alpha p ; p = m o r + beta p ; stop rule. This kernel keeps
+// the text of update_xp_body<T, ZDiag<MNT>, kDotsLocal> in its own body: as a
+// wrapper over update_xp_body, <float, false> allocated 66 VGPRs against 62
+// here (7 waves per SIMD against 8).
 template <typename T, bool MNT>
 __global__ __launch_bounds__(kBlock) void k_update_xp_pc(int64_t n, T *__restrict__ x,
                                                          T *__restrict__ p,
@@ -5895,117 +5922,11 @@ __global__ __launch_bounds__(kBlock) void k_update_xp_pc(int64_t n, T *__restric
       x[n - 1] = x[n - 1] + alpha * pv;
       p[n - 1] = m[n - 1] * r[n - 1] + beta * pv;
     }
-    pc_stop_rule(st, slot, rxr, rr, rzn);
-  }
-}
-
-// A partitioned preconditioned body's world {r.r, r.z} in the peer
-// transport's fused form: this rank's two double-length sums all-reduced
-// together under tag base + 2 (peerdev::world_sum2; the plain body's r.r
-// all-reduce, update_xp_body's PEER). false: the body stops (fault raised).
-template <typename T>
-__device__ __forceinline__ bool pc_world_pair(Dd<T> rd, Dd<T> zd, CgScalars<T> *st, int slot,
-                                              const PeerDev *P, T *rr, T *rzn) {
-  __shared__ double wres2[2];
-  __shared__ int wok2;
-  if (P->state->fault) {  // an earlier spin timed out: stop this body too
-    peer_fault(st, slot, P);
-    return false;
-  }
-  if (!peerdev::world_sum2(Dd<double>((double)rd.hi, (double)rd.lo),
-                           Dd<double>((double)zd.hi, (double)zd.lo),
-                           P->state->arb[slot & 1] + 2, *P, wres2, &wok2)) {
-    peer_fault(st, slot, P);
-    return false;
-  }
-  *rr = (T)wres2[0];
-  *rzn = (T)wres2[1];
-  return true;
-}
-// the next body's tag base (workgroup 0, thread 0, after the stop rule)
-__device__ __forceinline__ void pc_next_base(int slot, const PeerDev *P) {
-  const unsigned long long t = P->state->arb[slot & 1] + 2;
-  P->state->ar = t;
-  P->state->arb[(slot + 1) & 1] = t;
-}
-
-// mode 1 on a partitioned matrix: k_update_xp_pc statement for statement,
-// with the world {r.r, r.z} all-reduced here (D == 1) or read from the
-// scalar ring (D == 2: st->rrz, put there by the separate all-reduce step)
-template <typename T, int D>
-__device__ __forceinline__ void update_xp_pc_dist_body(int64_t n, T *__restrict__ x,
-                                                       T *__restrict__ p,
-                                                       const T *__restrict__ r,
-                                                       const T *__restrict__ m,
-                                                       CgScalars<T> *st, int slot, RedWs<T> *ws,
-                                                       int np_rr, int rev, const PeerDev *P) {
-  const int nxt = (slot + 1) & 3;
-  if (!st->active[slot]) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->active[nxt] = 0;
-    return;
-  }
-  __shared__ T red[8];
-  __shared__ T redz[8];
-  const T rxr = st->rxr[slot];
-  const T rz = st->rz[slot];
-  const T alpha = rz / st->pAp[slot];
-  T rr, rzn;
-  if constexpr (D == 2) {
-    rr = st->rrz[2 * slot];
-    rzn = st->rrz[2 * slot + 1];
-  } else {
-    const Dd<T> rd = sum_parts_dd(ws->rr_part, np_rr, red);
-    const Dd<T> zd = sum_parts_dd(ws->rz_part, np_rr, redz);
-    if (!pc_world_pair(rd, zd, st, slot, P, &rr, &rzn)) return;
-  }
-  const T beta = rzn / rz;
-  using V = typename Vec2<T>::V;
-  const int64_t n2 = n >> 1;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  V *x2 = reinterpret_cast<V *>(x);
-  V *p2 = reinterpret_cast<V *>(p);
-  const V *rv2 = reinterpret_cast<const V *>(r);
-  const V *m2 = reinterpret_cast<const V *>(m);
-  auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
-  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  for (; i + 3 * stride < n2; i += 4 * stride) {
-    V xv[4], pv[4], rv[4], mv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      xv[u] = x2[E(i + u * stride)];
-      pv[u] = p2[E(i + u * stride)];
-      rv[u] = rv2[E(i + u * stride)];
-      mv[u] = m2[E(i + u * stride)];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      xv[u].x = xv[u].x + alpha * pv[u].x;
-      xv[u].y = xv[u].y + alpha * pv[u].y;
-      pv[u].x = mv[u].x * rv[u].x + beta * pv[u].x;
-      pv[u].y = mv[u].y * rv[u].y + beta * pv[u].y;
-      x2[E(i + u * stride)] = xv[u];
-      p2[E(i + u * stride)] = pv[u];
-    }
-  }
-  for (; i < n2; i += stride) {
-    V xv = x2[E(i)], pv = p2[E(i)];
-    const V rv = rv2[E(i)];
-    const V mv = m2[E(i)];
-    xv.x = xv.x + alpha * pv.x;
-    xv.y = xv.y + alpha * pv.y;
-    pv.x = mv.x * rv.x + beta * pv.x;
-    pv.y = mv.y * rv.y + beta * pv.y;
-    x2[E(i)] = xv;
-    p2[E(i)] = pv;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (n & 1) {
-      const T pv = p[n - 1];
-      x[n - 1] = x[n - 1] + alpha * pv;
-      p[n - 1] = m[n - 1] * r[n - 1] + beta * pv;
-    }
-    pc_stop_rule(st, slot, rxr, rr, rzn);
-    if constexpr (D == 1) pc_next_base(slot, P);
+    st->rr[slot] = rr;  // the record
+    stop_rule(st, slot, rxr, [=](int) {
+      st->rxr[nxt] = rr;
+      st->rz[nxt] = rzn;
+    });
   }
 }
 template <typename T>
@@ -6016,7 +5937,7 @@ __global__ __launch_bounds__(kBlock) void k_update_xp_pc_peer(int64_t n, T *__re
                                                               CgScalars<T> *st, int slot,
                                                               RedWs<T> *ws, int np_rr, int rev,
                                                               PeerDev P) {
-  update_xp_pc_dist_body<T, 1>(n, x, p, r, m, st, slot, ws, np_rr, rev, &P);
+  update_xp_body<T, ZDiag<false>, kDotsPeer>(n, x, p, r, m, st, slot, ws, np_rr, rev, &P);
 }
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_update_xp_pc_ring(int64_t n, T *__restrict__ x,
@@ -6025,187 +5946,22 @@ __global__ __launch_bounds__(kBlock) void k_update_xp_pc_ring(int64_t n, T *__re
                                                               const T *__restrict__ m,
                                                               CgScalars<T> *st, int slot,
                                                               RedWs<T> *ws, int rev) {
-  update_xp_pc_dist_body<T, 2>(n, x, p, r, m, st, slot, ws, 0, rev, nullptr);
+  update_xp_body<T, ZDiag<false>, kDotsRing>(n, x, p, r, m, st, slot, ws, 0, rev, nullptr);
 }
 
 // mode 3: p_{k+1} = m o r + beta p_k into the next p buffer, the stop rule,
-// and in slot 3 (FLUSH) the group's x updates (update_p_defer_body's
-// single-device form; the alphas it applies are update_r_pc's rz / p.Ap)
-// D: the partitioned forms, as update_xp_pc_dist_body's
-template <typename T, bool FLUSH, bool SNT, bool MNT, int D = 0>
-__device__ __forceinline__ void update_p_defer_pc_body(int64_t n, T *__restrict__ x, const T *p,
-                                                       T *pn, const T *P0, const T *P1,
-                                                       const T *P2, const T *__restrict__ r,
-                                                       const T *__restrict__ m,
-                                                       CgScalars<T> *st, int slot, RedWs<T> *ws,
-                                                       int np_rr, int rev,
-                                                       const PeerDev *PD = nullptr) {
-  const int nxt = (slot + 1) & 3;
-  // the flag, rxr, rz and both dots' partials in one round trip
-  const auto *cst = (const __attribute__((address_space(4))) CgScalars<T> *)st;
-  const bool act = cst->active[slot] != 0;
-  const T rxr = cst->rxr[slot];
-  const T rz = cst->rz[slot];
-  T rr_st = T(0), rz_st = T(0);
-  if constexpr (D == 2) {
-    rr_st = cst->rrz[2 * slot];
-    rz_st = cst->rrz[2 * slot + 1];
-  }
-  Dd<T> pl[kPartsPerThread], plz[kPartsPerThread];
-  if constexpr (D != 2) {
-    parts_load_np(ws->rr_part, np_rr, pl);
-    parts_load_np(ws->rz_part, np_rr, plz);
-  }
-  using V = typename Vec2<T>::V;
-  const int64_t n2 = n >> 1;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
-  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const V *p2 = reinterpret_cast<const V *>(p);
-  const V *rv2 = reinterpret_cast<const V *>(r);
-  const V *m2 = reinterpret_cast<const V *>(m);
-  // the non-flushing body: this thread's first four elements of p_k, r and m
-  // go out with the partials, before beta (clamped; for n = 1 m's load reads
-  // r, which has the slack element a caller's m need not have)
-  V pv0[4], rv0[4], mv0[4];
-  if constexpr (!FLUSH) {
-    const V *m2f = n2 > 0 ? m2 : rv2;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int64_t j = E(min(i + u * stride, n2 > 0 ? n2 - 1 : 0));
-      pv0[u] = ldv<SNT, T>(p2 + j);
-      rv0[u] = ldv<SNT, T>(rv2 + j);
-      mv0[u] = ldv<MNT, T>(m2f + j);
-    }
-  }
-  if (!act) {
-    keep(rxr);
-    keep(rz);
-    if constexpr (D == 2) {
-      keep(rr_st);
-      keep(rz_st);
-    } else {
-      keep(pl);
-      keep(plz);
-    }
-    if constexpr (!FLUSH) {
-      keep(pv0);
-      keep(rv0);
-      keep(mv0);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->active[nxt] = 0;
-    return;
-  }
-  __shared__ T red[8];
-  __shared__ T redz[8];
-  T rr, rzn;
-  if constexpr (D == 2) {
-    rr = rr_st;
-    rzn = rz_st;
-  } else {
-    const Dd<T> rd = parts_sum_dd(pl, np_rr, red);
-    const Dd<T> zd = parts_sum_dd(plz, np_rr, redz);
-    rr = rd.value();
-    rzn = zd.value();
-    if constexpr (D == 1) {
-      if (!pc_world_pair(rd, zd, st, slot, PD, &rr, &rzn)) return;
-    }
-  }
-  const T beta = rzn / rz;
-  // slot-3 flush: alphas and skips of the group, written by earlier launches
-  T a[4] = {T(0), T(0), T(0), T(0)};
-  bool use[4] = {false, false, false, false};
-  if constexpr (FLUSH) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      a[t] = st->alpha[t];
-      use[t] = st->skip[t] == 0;
-    }
-  }
-  V *pn2 = reinterpret_cast<V *>(pn);
-  V *x2 = reinterpret_cast<V *>(x);
-  const V *Q[3] = {reinterpret_cast<const V *>(P0), reinterpret_cast<const V *>(P1),
-                   reinterpret_cast<const V *>(P2)};
-  auto body = [&](int64_t i) {
-    const V pv = ldv<SNT, T>(p2 + i);
-    const V rv = ldv<SNT, T>(rv2 + i);
-    const V mv = ldv<MNT, T>(m2 + i);
-    V q[3], xv;
-    if constexpr (FLUSH) {  // x and the old p buffers: not read again soon
-      xv = ldv<SNT, T>(x2 + i);
-#pragma unroll
-      for (int t = 0; t < 3; ++t) q[t] = ldv<SNT, T>(Q[t] + i);  // before pn (= P0) is written
-    }
-    V o;
-    o.x = mv.x * rv.x + beta * pv.x;
-    o.y = mv.y * rv.y + beta * pv.y;
-    if constexpr (FLUSH) {
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        if (use[t]) {
-          xv.x = xv.x + a[t] * q[t].x;
-          xv.y = xv.y + a[t] * q[t].y;
-        }
-      }
-      if (use[3]) {
-        xv.x = xv.x + a[3] * pv.x;
-        xv.y = xv.y + a[3] * pv.y;
-      }
-      stv<SNT, T>(x2 + i, xv);
-    }
-    pn2[i] = o;
-  };
-  if constexpr (!FLUSH) {
-    // the first block from the early loads (a block past the end: its
-    // clamped loads are not stored)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (i + u * stride < n2) {
-        V o;
-        o.x = mv0[u].x * rv0[u].x + beta * pv0[u].x;
-        o.y = mv0[u].y * rv0[u].y + beta * pv0[u].y;
-        pn2[E(i + u * stride)] = o;
-      }
-    }
-    i += 4 * stride;
-  }
-  for (; i + 3 * stride < n2; i += 4 * stride) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) body(E(i + u * stride));
-  }
-  for (; i < n2; i += stride) body(E(i));
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (n & 1) {
-      const T pv = p[n - 1];
-      if constexpr (FLUSH) {
-        T xv = x[n - 1];
-        const T *Ps[4] = {P0, P1, P2, p};
-        for (int t = 0; t < 4; ++t)
-          if (use[t]) xv = xv + a[t] * Ps[t][n - 1];
-        x[n - 1] = xv;
-      }
-      pn[n - 1] = m[n - 1] * r[n - 1] + beta * pv;
-    }
-    pc_stop_rule(st, slot, rxr, rr, rzn);
-    if constexpr (FLUSH) {
-      for (int t = 0; t < 4; ++t) st->ran[t] = 0;
-    } else {
-      st->ran[slot] = 1;
-    }
-    if constexpr (D == 1) pc_next_base(slot, PD);
-  }
-}
+// and in slot 3 (FLUSH) the group's x updates
 template <typename T, bool FLUSH>
 __global__ __launch_bounds__(kBlock) void k_update_p_defer_pc_peer(
     int64_t n, T *__restrict__ x, const T *p, T *pn, const T *P0, const T *P1, const T *P2,
     const T *__restrict__ r, const T *__restrict__ m, CgScalars<T> *st, int slot, RedWs<T> *ws,
     int np_rr, int rev, PeerDev PD) {
   if (stream_nt<T>(n))
-    update_p_defer_pc_body<T, FLUSH, true, false, 1>(n, x, p, pn, P0, P1, P2, r, m, st, slot, ws,
-                                                     np_rr, rev, &PD);
+    update_p_defer_body<T, ZDiag<false>, kDotsPeer, FLUSH, true>(n, x, p, pn, P0, P1, P2, r, m, st,
+        slot, ws, np_rr, rev, &PD);
   else
-    update_p_defer_pc_body<T, FLUSH, false, false, 1>(n, x, p, pn, P0, P1, P2, r, m, st, slot,
-                                                      ws, np_rr, rev, &PD);
+    update_p_defer_body<T, ZDiag<false>, kDotsPeer, FLUSH, false>(n, x, p, pn, P0, P1, P2, r, m, st,
+        slot, ws, np_rr, rev, &PD);
 }
 template <typename T, bool FLUSH>
 __global__ __launch_bounds__(kBlock) void k_update_p_defer_pc_ring(
@@ -6213,11 +5969,11 @@ __global__ __launch_bounds__(kBlock) void k_update_p_defer_pc_ring(
     const T *__restrict__ r, const T *__restrict__ m, CgScalars<T> *st, int slot, RedWs<T> *ws,
     int rev) {
   if (stream_nt<T>(n))
-    update_p_defer_pc_body<T, FLUSH, true, false, 2>(n, x, p, pn, P0, P1, P2, r, m, st, slot, ws,
-                                                     0, rev);
+    update_p_defer_body<T, ZDiag<false>, kDotsRing, FLUSH, true>(n, x, p, pn, P0, P1, P2, r, m, st,
+        slot, ws, 0, rev, nullptr);
   else
-    update_p_defer_pc_body<T, FLUSH, false, false, 2>(n, x, p, pn, P0, P1, P2, r, m, st, slot,
-                                                      ws, 0, rev);
+    update_p_defer_body<T, ZDiag<false>, kDotsRing, FLUSH, false>(n, x, p, pn, P0, P1, P2, r, m, st,
+        slot, ws, 0, rev, nullptr);
 }
 template <typename T, bool FLUSH, bool MNT>
 __global__ __launch_bounds__(kBlock) void k_update_p_defer_pc(
@@ -6225,11 +5981,11 @@ __global__ __launch_bounds__(kBlock) void k_update_p_defer_pc(
     const T *__restrict__ r, const T *__restrict__ m, CgScalars<T> *st, int slot, RedWs<T> *ws,
     int np_rr, int rev) {
   if (stream_nt<T>(n))
-    update_p_defer_pc_body<T, FLUSH, true, MNT>(n, x, p, pn, P0, P1, P2, r, m, st, slot, ws,
-                                                np_rr, rev);
+    update_p_defer_body<T, ZDiag<MNT>, kDotsLocal, FLUSH, true>(n, x, p, pn, P0, P1, P2, r, m, st,
+        slot, ws, np_rr, rev, nullptr);
   else
-    update_p_defer_pc_body<T, FLUSH, false, MNT>(n, x, p, pn, P0, P1, P2, r, m, st, slot, ws,
-                                                 np_rr, rev);
+    update_p_defer_body<T, ZDiag<MNT>, kDotsLocal, FLUSH, false>(n, x, p, pn, P0, P1, P2, r, m, st,
+        slot, ws, np_rr, rev, nullptr);
 }
 
 // Jacobi's m: out[i] = 1 / (sum of row i's entries with col == i). Rows may
@@ -6459,220 +6215,30 @@ __global__ __launch_bounds__(kBlock) void k_update_r_blk(int64_t n, double *r, d
     update_r_blk_body<BS, false, KP>(n, r, apz, W, st, slot, ws, np_pap, rev);
 }
 
-// mode 1: x = x + alpha p ; p = z + beta p ; stop rule (k_update_xp_pc with z
-// read from the Ap buffer where that kernel forms m o r)
+// mode 1: x = x + alpha p ; p = z + beta p ; stop rule, with z read from the
+// Ap buffer where k_update_r_blk stored it (ZStored)
 __global__ __launch_bounds__(kBlock) void k_update_xp_blk(int64_t n, double *__restrict__ x,
                                                           double *__restrict__ p,
                                                           const double *__restrict__ z,
                                                           CgScalars<double> *st, int slot,
                                                           RedWs<double> *ws, int np_rr,
                                                           int rev) {
-  const int nxt = (slot + 1) & 3;
-  if (!st->active[slot]) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->active[nxt] = 0;
-    return;
-  }
-  __shared__ double red[8];
-  __shared__ double redz[8];
-  const double rxr = st->rxr[slot];
-  const double rz = st->rz[slot];
-  const double alpha = rz / st->pAp[slot];
-  const double rr = sum_parts_dd(ws->rr_part, np_rr, red).value();
-  const double rzn = sum_parts_dd(ws->rz_part, np_rr, redz).value();
-  const double beta = rzn / rz;
-  const int64_t n2 = n >> 1;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  double2 *x2 = reinterpret_cast<double2 *>(x);
-  double2 *p2 = reinterpret_cast<double2 *>(p);
-  const double2 *z2 = reinterpret_cast<const double2 *>(z);
-  auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
-  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  for (; i + 3 * stride < n2; i += 4 * stride) {
-    double2 xv[4], pv[4], zv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      xv[u] = x2[E(i + u * stride)];
-      pv[u] = p2[E(i + u * stride)];
-      zv[u] = z2[E(i + u * stride)];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      xv[u].x = xv[u].x + alpha * pv[u].x;
-      xv[u].y = xv[u].y + alpha * pv[u].y;
-      pv[u].x = zv[u].x + beta * pv[u].x;
-      pv[u].y = zv[u].y + beta * pv[u].y;
-      x2[E(i + u * stride)] = xv[u];
-      p2[E(i + u * stride)] = pv[u];
-    }
-  }
-  for (; i < n2; i += stride) {
-    double2 xv = x2[E(i)], pv = p2[E(i)];
-    const double2 zv = z2[E(i)];
-    xv.x = xv.x + alpha * pv.x;
-    xv.y = xv.y + alpha * pv.y;
-    pv.x = zv.x + beta * pv.x;
-    pv.y = zv.y + beta * pv.y;
-    x2[E(i)] = xv;
-    p2[E(i)] = pv;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (n & 1) {
-      const double pv = p[n - 1];
-      x[n - 1] = x[n - 1] + alpha * pv;
-      p[n - 1] = z[n - 1] + beta * pv;
-    }
-    pc_stop_rule(st, slot, rxr, rr, rzn);
-  }
+  update_xp_body<double, ZStored, kDotsLocal>(n, x, p, z, nullptr, st, slot, ws, np_rr, rev,
+                                              nullptr);
 }
-
 // mode 3: p_{k+1} = z + beta p_k into the next p buffer, the stop rule, and in
-// slot 3 (FLUSH) the group's x updates (update_p_defer_pc_body's single-device
-// form with z read from the Ap buffer)
-template <bool FLUSH, bool SNT>
-__device__ __forceinline__ void update_p_defer_blk_body(int64_t n, double *__restrict__ x,
-                                                        const double *p, double *pn,
-                                                        const double *P0, const double *P1,
-                                                        const double *P2,
-                                                        const double *__restrict__ z,
-                                                        CgScalars<double> *st, int slot,
-                                                        RedWs<double> *ws, int np_rr, int rev) {
-  using T = double;
-  using V = double2;
-  const int nxt = (slot + 1) & 3;
-  // the flag, rxr, rz and both dots' partials in one round trip
-  const auto *cst = (const __attribute__((address_space(4))) CgScalars<T> *)st;
-  const bool act = cst->active[slot] != 0;
-  const T rxr = cst->rxr[slot];
-  const T rz = cst->rz[slot];
-  Dd<T> pl[kPartsPerThread], plz[kPartsPerThread];
-  parts_load_np(ws->rr_part, np_rr, pl);
-  parts_load_np(ws->rz_part, np_rr, plz);
-  const int64_t n2 = n >> 1;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  auto E = [&](int64_t j) { return rev ? n2 - 1 - j : j; };  // sweep direction
-  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const V *p2 = reinterpret_cast<const V *>(p);
-  const V *z2 = reinterpret_cast<const V *>(z);
-  // the non-flushing body: this thread's first four elements of p_k and z go
-  // out with the partials, before beta (clamped; for n = 1 one element past
-  // the end: both from the Ap buffer, which carries a slack element)
-  V pv0[4], zv0[4];
-  if constexpr (!FLUSH) {
-    const V *p2f = n2 > 0 ? p2 : z2;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int64_t j = n2 > 0 ? E(min(i + u * stride, n2 - 1)) : 0;
-      pv0[u] = ldv<SNT, T>(p2f + j);
-      zv0[u] = ldv<SNT, T>(z2 + j);
-    }
-  }
-  if (!act) {
-    keep(rxr);
-    keep(rz);
-    keep(pl);
-    keep(plz);
-    if constexpr (!FLUSH) {
-      keep(pv0);
-      keep(zv0);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->active[nxt] = 0;
-    return;
-  }
-  __shared__ T red[8];
-  __shared__ T redz[8];
-  const T rr = parts_sum_dd(pl, np_rr, red).value();
-  const T rzn = parts_sum_dd(plz, np_rr, redz).value();
-  const T beta = rzn / rz;
-  // slot-3 flush: alphas and skips of the group, written by earlier launches
-  T a[4] = {T(0), T(0), T(0), T(0)};
-  bool use[4] = {false, false, false, false};
-  if constexpr (FLUSH) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      a[t] = st->alpha[t];
-      use[t] = st->skip[t] == 0;
-    }
-  }
-  V *pn2 = reinterpret_cast<V *>(pn);
-  V *x2 = reinterpret_cast<V *>(x);
-  const V *Q[3] = {reinterpret_cast<const V *>(P0), reinterpret_cast<const V *>(P1),
-                   reinterpret_cast<const V *>(P2)};
-  auto body = [&](int64_t i) {
-    const V pv = ldv<SNT, T>(p2 + i);
-    const V zv = ldv<SNT, T>(z2 + i);
-    V q[3], xv;
-    if constexpr (FLUSH) {  // x and the old p buffers: not read again soon
-      xv = ldv<SNT, T>(x2 + i);
-#pragma unroll
-      for (int t = 0; t < 3; ++t) q[t] = ldv<SNT, T>(Q[t] + i);  // before pn (= P0) is written
-    }
-    V o;
-    o.x = zv.x + beta * pv.x;
-    o.y = zv.y + beta * pv.y;
-    if constexpr (FLUSH) {
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        if (use[t]) {
-          xv.x = xv.x + a[t] * q[t].x;
-          xv.y = xv.y + a[t] * q[t].y;
-        }
-      }
-      if (use[3]) {
-        xv.x = xv.x + a[3] * pv.x;
-        xv.y = xv.y + a[3] * pv.y;
-      }
-      stv<SNT, T>(x2 + i, xv);
-    }
-    pn2[i] = o;
-  };
-  if constexpr (!FLUSH) {
-    // the first block from the early loads (a block past the end: its
-    // clamped loads are not stored)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (i + u * stride < n2) {
-        V o;
-        o.x = zv0[u].x + beta * pv0[u].x;
-        o.y = zv0[u].y + beta * pv0[u].y;
-        pn2[E(i + u * stride)] = o;
-      }
-    }
-    i += 4 * stride;
-  }
-  for (; i + 3 * stride < n2; i += 4 * stride) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) body(E(i + u * stride));
-  }
-  for (; i < n2; i += stride) body(E(i));
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (n & 1) {
-      const T pv = p[n - 1];
-      if constexpr (FLUSH) {
-        T xv = x[n - 1];
-        const T *Ps[4] = {P0, P1, P2, p};
-        for (int t = 0; t < 4; ++t)
-          if (use[t]) xv = xv + a[t] * Ps[t][n - 1];
-        x[n - 1] = xv;
-      }
-      pn[n - 1] = z[n - 1] + beta * pv;
-    }
-    pc_stop_rule(st, slot, rxr, rr, rzn);
-    if constexpr (FLUSH) {
-      for (int t = 0; t < 4; ++t) st->ran[t] = 0;
-    } else {
-      st->ran[slot] = 1;
-    }
-  }
-}
+// slot 3 (FLUSH) the group's x updates
 template <bool FLUSH>
 __global__ __launch_bounds__(kBlock) void k_update_p_defer_blk(
     int64_t n, double *__restrict__ x, const double *p, double *pn, const double *P0,
     const double *P1, const double *P2, const double *__restrict__ z, CgScalars<double> *st,
     int slot, RedWs<double> *ws, int np_rr, int rev) {
   if (stream_nt<double>(n))
-    update_p_defer_blk_body<FLUSH, true>(n, x, p, pn, P0, P1, P2, z, st, slot, ws, np_rr, rev);
+    update_p_defer_body<double, ZStored, kDotsLocal, FLUSH, true>(n, x, p, pn, P0, P1, P2, z,
+        nullptr, st, slot, ws, np_rr, rev, nullptr);
   else
-    update_p_defer_blk_body<FLUSH, false>(n, x, p, pn, P0, P1, P2, z, st, slot, ws, np_rr, rev);
+    update_p_defer_body<double, ZStored, kDotsLocal, FLUSH, false>(n, x, p, pn, P0, P1, P2, z,
+        nullptr, st, slot, ws, np_rr, rev, nullptr);
 }
 
 // *dst = sum of part[0..np) in sum_parts order (partitioned runs: the local
@@ -7029,34 +6595,54 @@ hipError_t Launch<T>::spmv_dot_variant(int v, const CsrDev &A, const T *p, T *Ap
   }
   CGX_SPMV_SWITCH(vv);
 }
+// ---- the vector step of a three-kernel body (VecStep, cgx_internal.h).
+// update_r, update_xp and update_p_defer hold the only table from (z, the
+// dots' source, FLUSH, MNT, KP) to kernel. KP: the partials a thread loads
+// (np_pap <= KP kBlock). A preconditioned body sums its dots from partials
+// unless it reads the ring: np < 1 is refused there.
 template <typename T>
 hipError_t Launch<T>::update_r(int64_t n, T *r, const T *Ap, CgScalars<T> *st, int slot,
                                RedWs<T> *ws, hipStream_t s, bool fused, int np_pap, int rev,
-                               const T *rin, int rule, const PeerDev *peer) {
+                               const T *rin, int rule, const VecStep<T> &vs) {
+  if (vs.z) return hipErrorInvalidValue;  // block-Jacobi: blk_update_r
+  const int g = grid_elems(n, kGridUpdateR);
+#define CGX_UR_KP(LAUNCH)                       \
+  do {                                          \
+    if (np_pap <= 4 * kBlock) LAUNCH(4);        \
+    if (np_pap <= 8 * kBlock) LAUNCH(8);        \
+    LAUNCH(kPartsPerThread);                    \
+  } while (0)
+  if (vs.m) {  // z = m o r; on a partitioned matrix m through plain loads
+    if (fused || rule || rin) return hipErrorInvalidValue;
+    if (vs.ring) CGX_LAUNCH(k_update_r_pc_ring<T>, g, n, r, Ap, vs.m, st, slot, ws, rev);
+    if (np_pap < 1) return hipErrorInvalidValue;
+#define CGX_UR_PEER(KP)                                                                   \
+  CGX_LAUNCH((k_update_r_pc_peer<T, KP>), g, n, r, Ap, vs.m, st, slot, ws, np_pap, rev, *vs.peer)
+#define CGX_UR_PC(KP)                                                                     \
+  do {                                                                                    \
+    if (vs.m_nt)                                                                          \
+      CGX_LAUNCH((k_update_r_pc<T, true, KP>), g, n, r, Ap, vs.m, st, slot, ws, np_pap, rev); \
+    CGX_LAUNCH((k_update_r_pc<T, false, KP>), g, n, r, Ap, vs.m, st, slot, ws, np_pap, rev);  \
+  } while (0)
+    if (vs.peer) CGX_UR_KP(CGX_UR_PEER);
+    CGX_UR_KP(CGX_UR_PC);
+#undef CGX_UR_PEER
+#undef CGX_UR_PC
+  }
   if (!rin) rin = r;
-  if (peer) {
+  if (vs.ring) np_pap = 0;  // the world p.Ap is in st->pAp[slot]
+  if (vs.peer) {
     if (fused || rule || rin != r) return hipErrorInvalidValue;
-    CGX_GGL((k_update_r_peer<T>), dim3(grid_elems(n, kGridUpdateR)), dim3(kBlock), 0,
-                       s, n, r, Ap, st, slot, ws, np_pap, rev, *peer);
-    return hipGetLastError();
+    CGX_LAUNCH(k_update_r_peer<T>, g, n, r, Ap, st, slot, ws, np_pap, rev, *vs.peer);
   }
-  if (fused) {
-    CGX_GGL((k_update_r<T, true>), dim3(grid_elems(n, kMaxGrid)), dim3(kBlock), 0, s,
-                       n, rin, r,
-                       Ap, st, slot, ws, 0, 0, 0);
-  } else {
-    const int g = grid_elems(n, kGridUpdateR);
-    if (np_pap <= 4 * kBlock)
-      CGX_GGL((k_update_r<T, false, 4>), dim3(g), dim3(kBlock), 0, s, n, rin, r, Ap, st, slot,
-              ws, np_pap, rev, rule);
-    else if (np_pap <= 8 * kBlock)
-      CGX_GGL((k_update_r<T, false, 8>), dim3(g), dim3(kBlock), 0, s, n, rin, r, Ap, st, slot,
-              ws, np_pap, rev, rule);
-    else
-      CGX_GGL((k_update_r<T, false>), dim3(g), dim3(kBlock), 0, s, n, rin, r, Ap, st, slot, ws,
-              np_pap, rev, rule);
-  }
-  return hipGetLastError();
+  if (fused)
+    CGX_LAUNCH((k_update_r<T, true>), grid_elems(n, kMaxGrid), n, rin, r, Ap, st, slot, ws, 0, 0,
+               0);
+#define CGX_UR_PLAIN(KP)                                                                  \
+  CGX_LAUNCH((k_update_r<T, false, KP>), g, n, rin, r, Ap, st, slot, ws, np_pap, rev, rule)
+  CGX_UR_KP(CGX_UR_PLAIN);
+#undef CGX_UR_PLAIN
+#undef CGX_UR_KP
 }
 
 // ---- mode 4 (fused deferred-x iteration): k_spmv_fd is instantiated for
@@ -7380,11 +6966,27 @@ hipError_t Launch<T>::flush_x(int64_t n, T *x, const T *p, CgScalars<T> *st, int
 template <typename T>
 hipError_t Launch<T>::update_xp(int64_t n, T *x, T *p, const T *r, CgScalars<T> *st,
                                 int slot, RedWs<T> *ws, int np_rr, hipStream_t s, int rev,
-                                const PeerDev *peer) {
-  if (peer)
-    CGX_LAUNCH(k_update_xp_peer<T>, grid_elems(n, kGridUpdateP), n, x, p, r, st, slot, ws, np_rr,
-               rev, *peer);
-  CGX_LAUNCH(k_update_xp<T>, grid_elems(n, kGridUpdateP), n, x, p, r, st, slot, ws, np_rr, rev);
+                                const VecStep<T> &vs) {
+  const int g = grid_elems(n, kGridUpdateP);
+  if (vs.z) {  // block-Jacobi: f64, one device
+    if constexpr (std::is_same_v<T, double>) {
+      if (vs.m || vs.peer || vs.ring || np_rr < 1) return hipErrorInvalidValue;
+      CGX_LAUNCH(k_update_xp_blk, g, n, x, p, vs.z, st, slot, ws, np_rr, rev);
+    }
+    return hipErrorInvalidValue;
+  }
+  if (vs.m) {
+    if (vs.ring) CGX_LAUNCH(k_update_xp_pc_ring<T>, g, n, x, p, r, vs.m, st, slot, ws, rev);
+    if (np_rr < 1) return hipErrorInvalidValue;
+    if (vs.peer)
+      CGX_LAUNCH(k_update_xp_pc_peer<T>, g, n, x, p, r, vs.m, st, slot, ws, np_rr, rev, *vs.peer);
+    if (vs.m_nt)
+      CGX_LAUNCH((k_update_xp_pc<T, true>), g, n, x, p, r, vs.m, st, slot, ws, np_rr, rev);
+    CGX_LAUNCH((k_update_xp_pc<T, false>), g, n, x, p, r, vs.m, st, slot, ws, np_rr, rev);
+  }
+  if (vs.ring) np_rr = 0;  // the world r.r is in st->rr[slot]
+  if (vs.peer) CGX_LAUNCH(k_update_xp_peer<T>, g, n, x, p, r, st, slot, ws, np_rr, rev, *vs.peer);
+  CGX_LAUNCH(k_update_xp<T>, g, n, x, p, r, st, slot, ws, np_rr, rev);
 }
 
 // ---- batched CG ----------------------------------------------
@@ -7509,23 +7111,33 @@ hipError_t Launch<T>::batch_update_xp(int64_t n, int width, T *X, int64_t ldx, T
 template <typename T>
 hipError_t Launch<T>::update_p_defer(int64_t n, T *x, const T *p, T *pn, T *const P[4],
                                      const T *r, CgScalars<T> *st, int slot, RedWs<T> *ws,
-                                     int np_rr, hipStream_t s, int rev, const PeerDev *peer) {
-  if (peer && slot == 3)
-    CGX_LAUNCH((k_update_p_defer_peer<T, true>), grid_elems(n, kGridUpdateP), n, x, p, pn,
-               (const T *)P[0], (const T *)P[1], (const T *)P[2], r, st, slot, ws, np_rr, rev,
-               *peer);
-  if (peer)
-    CGX_LAUNCH((k_update_p_defer_peer<T, false>), grid_elems(n, kGridUpdateP), n, x, p, pn,
-               (const T *)P[0], (const T *)P[1], (const T *)P[2], r, st, slot, ws, np_rr, rev,
-               *peer);
-  if (slot == 3) {
-    CGX_LAUNCH((k_update_p_defer<T, true>), grid_elems(n, kGridUpdateP), n, x, p, pn,
-               (const T *)P[0],
-               (const T *)P[1], (const T *)P[2], r, st, slot, ws, np_rr, rev);
-  }
-  CGX_LAUNCH((k_update_p_defer<T, false>), grid_elems(n, kGridUpdateP), n, x, p, pn,
-             (const T *)P[0],
-             (const T *)P[1], (const T *)P[2], r, st, slot, ws, np_rr, rev);
+                                     int np_rr, hipStream_t s, int rev, const VecStep<T> &vs) {
+  const int g = grid_elems(n, kGridUpdateP);
+  auto table = [&](auto flush) -> hipError_t {  // slot 3 flushes the group's x updates
+    constexpr bool FL = decltype(flush)::value;
+#define CGX_UPD(K, ...)                                                                   \
+  CGX_LAUNCH(K, g, n, x, p, pn, (const T *)P[0], (const T *)P[1], (const T *)P[2], __VA_ARGS__)
+    if (vs.z) {  // block-Jacobi: f64, one device
+      if constexpr (std::is_same_v<T, double>) {
+        if (vs.m || vs.peer || vs.ring || np_rr < 1) return hipErrorInvalidValue;
+        CGX_UPD(k_update_p_defer_blk<FL>, vs.z, st, slot, ws, np_rr, rev);
+      }
+      return hipErrorInvalidValue;
+    }
+    if (vs.m) {
+      if (vs.ring) CGX_UPD((k_update_p_defer_pc_ring<T, FL>), r, vs.m, st, slot, ws, rev);
+      if (np_rr < 1) return hipErrorInvalidValue;
+      if (vs.peer)
+        CGX_UPD((k_update_p_defer_pc_peer<T, FL>), r, vs.m, st, slot, ws, np_rr, rev, *vs.peer);
+      if (vs.m_nt) CGX_UPD((k_update_p_defer_pc<T, FL, true>), r, vs.m, st, slot, ws, np_rr, rev);
+      CGX_UPD((k_update_p_defer_pc<T, FL, false>), r, vs.m, st, slot, ws, np_rr, rev);
+    }
+    const int np = vs.ring ? 0 : np_rr;  // ring: the world r.r is in st->rr[slot]
+    if (vs.peer) CGX_UPD((k_update_p_defer_peer<T, FL>), r, st, slot, ws, np, rev, *vs.peer);
+    CGX_UPD((k_update_p_defer<T, FL>), r, st, slot, ws, np, rev);
+#undef CGX_UPD
+  };
+  return slot == 3 ? table(std::true_type{}) : table(std::false_type{});
 }
 template <typename T>
 hipError_t Launch<T>::flush_defer(int64_t n, T *x, T *const P[4], CgScalars<T> *st,
@@ -7538,108 +7150,12 @@ hipError_t Launch<T>::flush_defer(int64_t n, T *x, T *const P[4], CgScalars<T> *
   CGX_GGL(k_mark_defer<T>, dim3(1), dim3(1), 0, s, st);
   return hipGetLastError();
 }
-// ---- diagonal preconditioning: the grids of the kernels they mirror
+// ---- diagonal preconditioning: the grid of the p updates
 template <typename T>
 hipError_t Launch<T>::pc_init(int64_t n, const T *r, const T *m, T *p, CgScalars<T> *st,
-                              RedWs<T> *ws, hipStream_t s) {
+                              RedWs<T> *ws, hipStream_t s, bool dist) {
+  if (dist) CGX_LAUNCH(k_pc_init_dist<T>, grid_elems(n, kGridUpdateP), n, r, m, p, st, ws);
   CGX_LAUNCH(k_pc_init<T>, grid_elems(n, kGridUpdateP), n, r, m, p, st, ws);
-}
-template <typename T>
-hipError_t Launch<T>::update_r_pc(int64_t n, T *r, const T *Ap, const T *m, CgScalars<T> *st,
-                                  int slot, RedWs<T> *ws, hipStream_t s, int np_pap, int rev,
-                                  bool m_nt) {
-  if (np_pap < 1) return hipErrorInvalidValue;
-  const int g = grid_elems(n, kGridUpdateR);
-#define CGX_URPC(MNT, KP)                                                                 \
-  CGX_LAUNCH((k_update_r_pc<T, MNT, KP>), g, n, r, Ap, m, st, slot, ws, np_pap, rev)
-  if (np_pap <= 4 * kBlock) {
-    if (m_nt) CGX_URPC(true, 4);
-    CGX_URPC(false, 4);
-  }
-  if (np_pap <= 8 * kBlock) {
-    if (m_nt) CGX_URPC(true, 8);
-    CGX_URPC(false, 8);
-  }
-  if (m_nt) CGX_URPC(true, kPartsPerThread);
-  CGX_URPC(false, kPartsPerThread);
-#undef CGX_URPC
-}
-template <typename T>
-hipError_t Launch<T>::update_xp_pc(int64_t n, T *x, T *p, const T *r, const T *m,
-                                   CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr,
-                                   hipStream_t s, int rev, bool m_nt) {
-  if (np_rr < 1) return hipErrorInvalidValue;
-  if (m_nt)
-    CGX_LAUNCH((k_update_xp_pc<T, true>), grid_elems(n, kGridUpdateP), n, x, p, r, m, st, slot, ws,
-               np_rr, rev);
-  CGX_LAUNCH((k_update_xp_pc<T, false>), grid_elems(n, kGridUpdateP), n, x, p, r, m, st, slot, ws,
-             np_rr, rev);
-}
-template <typename T>
-hipError_t Launch<T>::update_p_defer_pc(int64_t n, T *x, const T *p, T *pn, T *const P[4],
-                                        const T *r, const T *m, CgScalars<T> *st, int slot,
-                                        RedWs<T> *ws, int np_rr, hipStream_t s, int rev,
-                                        bool m_nt) {
-  if (np_rr < 1) return hipErrorInvalidValue;
-#define CGX_UPPC(FL, MNT)                                                                  \
-  CGX_LAUNCH((k_update_p_defer_pc<T, FL, MNT>), grid_elems(n, kGridUpdateP), n, x, p, pn,  \
-             (const T *)P[0], (const T *)P[1], (const T *)P[2], r, m, st, slot, ws, np_rr, rev)
-  if (slot == 3) {
-    if (m_nt) CGX_UPPC(true, true);
-    CGX_UPPC(true, false);
-  }
-  if (m_nt) CGX_UPPC(false, true);
-  CGX_UPPC(false, false);
-#undef CGX_UPPC
-}
-// the partitioned forms: peer != nullptr the peer transport's fused form
-// (np the local partials), else the world values from the scalar ring
-template <typename T>
-hipError_t Launch<T>::pc_init_dist(int64_t n, const T *r, const T *m, T *p, CgScalars<T> *st,
-                                   RedWs<T> *ws, hipStream_t s) {
-  CGX_LAUNCH(k_pc_init_dist<T>, grid_elems(n, kGridUpdateP), n, r, m, p, st, ws);
-}
-template <typename T>
-hipError_t Launch<T>::update_r_pc_dist(int64_t n, T *r, const T *Ap, const T *m,
-                                       CgScalars<T> *st, int slot, RedWs<T> *ws, hipStream_t s,
-                                       int np_pap, int rev, const PeerDev *peer) {
-  const int g = grid_elems(n, kGridUpdateR);
-  if (!peer) CGX_LAUNCH(k_update_r_pc_ring<T>, g, n, r, Ap, m, st, slot, ws, rev);
-  if (np_pap < 1) return hipErrorInvalidValue;
-  if (np_pap <= 4 * kBlock)
-    CGX_LAUNCH((k_update_r_pc_peer<T, 4>), g, n, r, Ap, m, st, slot, ws, np_pap, rev, *peer);
-  if (np_pap <= 8 * kBlock)
-    CGX_LAUNCH((k_update_r_pc_peer<T, 8>), g, n, r, Ap, m, st, slot, ws, np_pap, rev, *peer);
-  CGX_LAUNCH((k_update_r_pc_peer<T, kPartsPerThread>), g, n, r, Ap, m, st, slot, ws, np_pap, rev,
-             *peer);
-}
-template <typename T>
-hipError_t Launch<T>::update_xp_pc_dist(int64_t n, T *x, T *p, const T *r, const T *m,
-                                        CgScalars<T> *st, int slot, RedWs<T> *ws, int np_rr,
-                                        hipStream_t s, int rev, const PeerDev *peer) {
-  const int g = grid_elems(n, kGridUpdateP);
-  if (!peer) CGX_LAUNCH(k_update_xp_pc_ring<T>, g, n, x, p, r, m, st, slot, ws, rev);
-  if (np_rr < 1) return hipErrorInvalidValue;
-  CGX_LAUNCH(k_update_xp_pc_peer<T>, g, n, x, p, r, m, st, slot, ws, np_rr, rev, *peer);
-}
-template <typename T>
-hipError_t Launch<T>::update_p_defer_pc_dist(int64_t n, T *x, const T *p, T *pn, T *const P[4],
-                                             const T *r, const T *m, CgScalars<T> *st, int slot,
-                                             RedWs<T> *ws, int np_rr, hipStream_t s, int rev,
-                                             const PeerDev *peer) {
-  const int g = grid_elems(n, kGridUpdateP);
-  if (!peer && slot == 3)
-    CGX_LAUNCH((k_update_p_defer_pc_ring<T, true>), g, n, x, p, pn, (const T *)P[0],
-               (const T *)P[1], (const T *)P[2], r, m, st, slot, ws, rev);
-  if (!peer)
-    CGX_LAUNCH((k_update_p_defer_pc_ring<T, false>), g, n, x, p, pn, (const T *)P[0],
-               (const T *)P[1], (const T *)P[2], r, m, st, slot, ws, rev);
-  if (np_rr < 1) return hipErrorInvalidValue;
-  if (slot == 3)
-    CGX_LAUNCH((k_update_p_defer_pc_peer<T, true>), g, n, x, p, pn, (const T *)P[0],
-               (const T *)P[1], (const T *)P[2], r, m, st, slot, ws, np_rr, rev, *peer);
-  CGX_LAUNCH((k_update_p_defer_pc_peer<T, false>), g, n, x, p, pn, (const T *)P[0],
-             (const T *)P[1], (const T *)P[2], r, m, st, slot, ws, np_rr, rev, *peer);
 }
 template <typename T>
 hipError_t Launch<T>::finalize2(const T *part_a, const T *part_b, int np, T *dst, hipStream_t s) {
@@ -7711,23 +7227,6 @@ hipError_t blk_update_r(int64_t n, int bs, double *r, double *apz, const double 
   }
 #undef CGX_URB
   return hipErrorInvalidValue;
-}
-hipError_t blk_update_xp(int64_t n, double *x, double *p, const double *z, CgScalars<double> *st,
-                         int slot, RedWs<double> *ws, int np_rr, hipStream_t s, int rev) {
-  if (np_rr < 1) return hipErrorInvalidValue;
-  CGX_LAUNCH(k_update_xp_blk, Launch<double>::grid_elems(n, kGridUpdateP), n, x, p, z, st, slot,
-             ws, np_rr, rev);
-}
-hipError_t blk_update_p_defer(int64_t n, double *x, const double *p, double *pn,
-                              double *const P[4], const double *z, CgScalars<double> *st,
-                              int slot, RedWs<double> *ws, int np_rr, hipStream_t s, int rev) {
-  if (np_rr < 1) return hipErrorInvalidValue;
-  const int g = Launch<double>::grid_elems(n, kGridUpdateP);
-  if (slot == 3)
-    CGX_LAUNCH(k_update_p_defer_blk<true>, g, n, x, p, pn, (const double *)P[0],
-               (const double *)P[1], (const double *)P[2], z, st, slot, ws, np_rr, rev);
-  CGX_LAUNCH(k_update_p_defer_blk<false>, g, n, x, p, pn, (const double *)P[0],
-             (const double *)P[1], (const double *)P[2], z, st, slot, ws, np_rr, rev);
 }
 
 template <typename T>

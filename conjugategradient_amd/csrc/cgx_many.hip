@@ -283,7 +283,7 @@ __device__ __forceinline__ void many_refuse(const ManyArgs &a, int s) {
 // doubles of LDS, the gather source. red: the workgroup's reduction stagings.
 //
 // kManyDiag: diagonal preconditioning (cgx_many_set_precond), statement for statement
-// as k_pc_init, update_r_pc_body, k_update_xp_pc and pc_stop_rule
+// as k_pc_init, update_r_body with ZDiag, k_update_xp_pc and stop_rule
 // (cgx_kernels.hip): z_i = m_i * r_i, rounded, never stored beyond the body
 // that forms it (it takes Ap's register once r is updated); alpha = rz / p.Ap,
 // beta = rz' / rz, r.r and r.z summed behind one barrier, so a body keeps its
@@ -436,7 +436,7 @@ __device__ __forceinline__ void many_cg_body(const ManyArgs &a, double *p, doubl
       const double pAp = Team::sum(acc, red, 0);
       const double alpha = (PCD ? rz : rxr) / pAp;
       // r -= alpha Ap and r.r (k_update_r); PC: r.z in the same sweep, z
-      // kept where Ap was (update_r_pc_body)
+      // kept where Ap was (update_r_body, ZDiag)
       acc = Dd<double>(0.0);
       double rr, rzn = 0.0;
       if constexpr (BK) {  // (update_r_blk_body)

@@ -15,8 +15,9 @@ import pytest
 import conjugategradient_amd as cga
 from conjugategradient_amd._native import check, lib
 from conjugategradient_amd.workloads import node_mixed
-from tests import bj_model
+from tests import bj_model, cg_model
 from tests import block_pcg_systems as S
+from tests.test_gpu_pcg import _tridiag5
 
 pytestmark = pytest.mark.gpu
 
@@ -187,6 +188,10 @@ def test_solve_is_the_models_bit_for_bit(queue, name, mode):
 
 
 # 3 -- cross-pins that need no model -------------------------------------------
+# the matrices of test_gpu_pcg.py::test_tiny_systems
+TINY = [np.array([[4.0]]), np.array([[4.0, 1.0], [1.0, 3.0]]), _tridiag5()]
+
+
 @pytest.mark.parametrize("bs", range(2, 9))
 def test_given_diagonal_w_is_the_diagonal_solver_and_identity_the_plain_one(queue, bs):
     """GIVEN with a W whose only entries are its diagonal is
@@ -212,6 +217,56 @@ def test_given_diagonal_w_is_the_diagonal_solver_and_identity_the_plain_one(queu
         _same(blk, dia)
         _same(ident[:4], plain[:4])
         assert ident[4] == ident[3]  # r.z is r.r
+
+
+def _start_residuals(rp, cl, vl, b, W, bodies):
+    """r at the start of bodies 1 .. `bodies`, by bj_model.cg's statements."""
+    r = np.array(b, np.float64)
+    p = bj_model.block_apply(W, r)
+    rz = cg_model.dot(r, p)[0]
+    out = []
+    for _ in range(bodies):
+        out.append(r)
+        Ap = cg_model.spmv(rp, cl, vl, p)
+        r = r - (rz / cg_model.dot(p, Ap)[0]) * Ap
+        z = bj_model.block_apply(W, r)
+        rzn = cg_model.dot(r, z)[0]
+        p = z + (rzn / rz) * p
+        rz = rzn
+    return out
+
+
+@pytest.mark.parametrize("dense", TINY, ids=["n1", "n2", "n5"])
+@pytest.mark.parametrize("mode", [1, 3])
+def test_tiny_systems_given_diagonal_w_and_identity(queue, dense, mode):
+    """The cross-pins of the test above on test_gpu_pcg.py::test_tiny_systems'
+    matrices (n = 1, 2, 5; b_i = i + 1), bs = 1, 2, 3 (n = 1, 2: one partial
+    block), 1 .. n bodies: the vector kernels' n >> 1 == 0 clamped loads and
+    their odd-n tail with z read from the z buffer. No body starts from an r
+    with a zero entry (asserted on the model's r), so no -0.0 can differ."""
+    n = len(dense)
+    r, c = np.nonzero(dense)
+    rp = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=n))]).astype(np.int32)
+    cl, vl = c.astype(np.int32), dense[r, c]
+    m = cga.Matrix(queue, vl, cl, rp)
+    b = np.arange(1, n + 1, dtype=np.float64)
+    d = np.random.default_rng(n).uniform(0.5, 2.0, n) / np.diag(dense)
+    with Solver(queue, m, mode) as s:
+        for bs in (1, 2, 3):
+            Wd = np.zeros((n, bs))
+            Wd[np.arange(n), np.arange(n) % bs] = d
+            Wi = (Wd != 0).astype(np.float64)
+            for W in (Wd, Wi):
+                assert all((rk != 0).all() for rk in _start_residuals(rp, cl, vl, b, W, n))
+            for bodies in range(1, n + 1):
+                blk = s.block(B.Given, bs, Wd).solve(b, 0.0, bodies)
+                ident = s.block(B.Given, bs, Wi).solve(b, 0.0, bodies)
+                dia = s.diag(P.Diagonal, d).solve(b, 0.0, bodies)
+                plain = s.diag(P.None_).solve(b, 0.0, bodies, rz=False)
+                assert blk[1] == bodies
+                _same(blk, dia)
+                _same(ident[:4], plain[:4])
+                assert ident[4] == ident[3]  # r.z is r.r
 
 
 def test_block_jacobi_of_one_row_is_jacobi(queue):

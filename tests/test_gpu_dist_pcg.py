@@ -122,6 +122,27 @@ def test_both_peer_forms(nproc):
     assert _bits(rf["steps"][0]) == _bits(ro["steps"][1])
 
 
+def test_fused_peer_form_with_odd_local_rows():
+    """p2d (33 x 31 = 1,023 rows) on 3 ranks: 341 rows each, so the vector
+    kernels' odd-n tail runs in the peer transport's fused form in modes 1 and
+    3 (p3d splits into even blocks on 2, 3 and 8 ranks; the ring form has odd
+    blocks in test_jacobi_30_bodies_against_checker's p2d x 2, 512 + 511, and
+    in test_to_tolerance_where_plain_cg_hits_the_cap). The checker and bounds
+    of test_jacobi_30_bodies_against_checker."""
+    r = _launch(3, "host-peer", "p2d", J30, FUSED)
+    assert r["peer_form"] == [[3, 0]] * 3, r["peer_form"]
+    one, three = r["steps"][:2]
+    for s, mode in ((one, 1), (three, 3)):
+        print(f"p2d x3 fused peer mode {mode}: rel {s['rel']:.3e}, r.r {s['rxr']:.17g} "
+              f"(checker {s['ref_rxr']:.17g}), r.z {s['rz']:.17g} (checker {s['ref_rz']:.17g})")
+        assert s["modes_run"] == [mode] * 3
+        assert s["bodies"] == s["ref_bodies"] == 30
+        assert s["rel"] <= 1e-13
+        assert s["rxr"] == pytest.approx(s["ref_rxr"], rel=1e-9)
+        assert s["rz"] == pytest.approx(s["ref_rz"], rel=1e-9)
+    assert _bits(three) == _bits(one)
+
+
 # 4, 5 ----------------------------------------------------------------------
 ID45 = "plain@1@45,ones@1@45,plain@3@45,ones@3@45"
 
